@@ -8,15 +8,25 @@ library's own batch signer, firedancer_amd/workload.py).  With N GPUs each
 rank verifies its own shard (different signatures, no collective: weak
 scaling); value = signatures verified by all ranks / max-over-ranks time.
 
-Printed on rank 0 as one JSON line, with:
+Printed on rank 0 as one JSON line.  A plain run sets up, warms up, times
+the K steps and prints value and ms_per_step; everything else the benchmark
+measures or checks runs only with --full (the fields are null otherwise):
   roofline      INT32 VALU roofline of the dominant kernel (dsm), from the
                 SURVEY.md §8(d) frozen per-verify op count and the kernel's
                 mean duration measured with HIP events on its stream
   cpu_baseline  the reference's own fd_ed25519_verify (compiled from its
                 sources into oracle/_ref) on this host's cores, over a bounded
                 sample of the same workload (rank 0, N=1 only)
+  and the verdict check against the class labels, the host-fed stream, the
+  C1 / C3 / C4 / C5 legs.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--full] [--dump-outputs DIR]
+
+--dump-outputs DIR writes the verdict codes of the last timed step (what the
+caller of fd_ed25519_hip_verify_dev receives: int8[n], stored as float32) to
+DIR/verdicts.npy (DIR/verdicts_rank<r>.npy with several ranks).  The
+workload is seeded, so two runs with the same arguments verify the same
+signatures.
 
 With --gpus N > 1 and no launcher environment (WORLD_SIZE unset), bench.py
 starts its N ranks itself, as child processes created before anything
@@ -1069,11 +1079,31 @@ def pmc_valu_per_sig():
         return None
 
 
+DUMP_MAX = 8 << 20   # codes dumped by all ranks together (32 MB as float32)
+
+
+def dump_outputs(path, codes, rank, world):
+    """--dump-outputs: the last timed step's verdict codes of this rank, as
+    float32; of more than this rank's share of DUMP_MAX codes a fixed
+    (seeded) sample, in index order."""
+    cap = DUMP_MAX // world
+    if codes.size > cap:
+        codes = codes[np.sort(np.random.default_rng(0).choice(codes.size, cap, replace=False))]
+    os.makedirs(path, exist_ok=True)
+    np.save(os.path.join(path, "verdicts.npy" if world == 1 else f"verdicts_rank{rank}.npy"), codes.astype(np.float32))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=2)
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also: the verdict check against the class labels, per-kernel "
+                         "durations and the roofline, the CPU baseline, the host-fed stream and the C1 / C3 / C4 / "
+                         "C5 legs (each still subject to its own option below); off: the timed steps only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the verdict codes of the last timed step to DIR/verdicts.npy (float32)")
     ap.add_argument("--config", default="C2")
     ap.add_argument("--n", type=int, default=0, help="signatures per GPU (default: the config's)")
     ap.add_argument("--seed", type=int, default=None,
@@ -1138,6 +1168,9 @@ def main():
     ap.add_argument("--allow-shared-device", action="store_true",
                     help="let ranks share a GPU (one-GPU rehearsal of --gpus N; n_gpus then counts devices)")
     args = ap.parse_args()
+    if not args.full:   # a plain run: the timed steps and the result line, none of the other legs
+        args.no_cpu_baseline = True
+        args.host_reps = args.c4_signatures = args.latency_txns = args.deployed_txns = 0
     # read by the HIP runtime when it starts (the first HIP call, below):
     # the latency-mode slots each get a hardware queue instead of pairing up
     # on HIP's default 4 (a batch on a shared queue waits for the one ahead)
@@ -1261,53 +1294,58 @@ def main():
     t1 = time.perf_counter()
     barrier(world)
     elapsed = allreduce_max(t1 - t0, world)
+    if args.dump_outputs and args.steps > 0:
+        dump_outputs(args.dump_outputs, outs[(args.steps - 1) % len(engines)].download(np.int8, n), rank, world)
     mism_inflight = 0
     used = {s % len(engines) for s in range(max(args.warmup, args.steps))}   # K or W below the depth: some idle
     for i, o in enumerate(outs):
         if o is wl.out:
             continue
-        if i in used:
+        if i in used and args.full:
             mism_inflight += int((o.download(np.int8, n) != wl.expect.download(np.int8, n)).sum())
         o.free()
     for e in engines:
         if e is not eng:
             e.close()
-    # per-kernel durations: a separate pass of the same steps with HIP events
-    # around each phase on the engine stream (the phases then run in sequence;
-    # in the timed region above a chunk's decode overlaps its hash + scalar,
-    # dsm runs alone either way)
-    eng.timing(True)
-    for _ in range(args.steps):
-        wl.verify()
-    eng.sync()
-    phase_ms, launches = eng.timing_read()
-    eng.timing(False)
-
-    # full-size verdict check: every code equals the class label's reference code
-    out = wl.out.download(np.int8, n)
-    expect = wl.expect.download(np.int8, n)
-    mism = int((out != expect).sum()) + mism_inflight
-    mism_all = int(allreduce_sum(mism, world))
-    if mism:
-        log(f"[rank {rank}] VERDICT MISMATCH on {mism} of {n} signatures")
-
     total = world * n * args.steps
     value = total / elapsed
     ms_step = elapsed * 1e3 / args.steps
 
-    # roofline (dsm = dominant kernel)
-    ops = workload.ops_per_verify(wl.sizes)
-    clock = eng.clock_mhz() * 1e6
-    peak = clock * info["cu_cnt"] * 64 * 2 / 1e12
-    per_launch = {k: v / max(launches, 1) for k, v in phase_ms.items()}
-    # a launch is one chunk of at most max_chunk signatures: ops per launch
-    # are the step's ops over its chunk count
-    chunks = -(-n // info["max_chunk"])
-    dsm_ops = float(ops["dsm"].sum()) / chunks
-    achieved = dsm_ops / (per_launch["dsm"] * 1e-3) / 1e12 if per_launch["dsm"] > 0 else None
-    path_ms = sum(per_launch.values())
-    path_ops = float(ops["total"].sum()) / chunks
-    path_achieved = path_ops / (path_ms * 1e-3) / 1e12 if path_ms > 0 else None
+    out = expect = per_launch = None
+    mism_all = 0
+    if args.full:
+        # per-kernel durations: a separate pass of the same steps with HIP events
+        # around each phase on the engine stream (the phases then run in sequence;
+        # in the timed region above a chunk's decode overlaps its hash + scalar,
+        # dsm runs alone either way)
+        eng.timing(True)
+        for _ in range(args.steps):
+            wl.verify()
+        eng.sync()
+        phase_ms, launches = eng.timing_read()
+        eng.timing(False)
+
+        # full-size verdict check: every code equals the class label's reference code
+        out = wl.out.download(np.int8, n)
+        expect = wl.expect.download(np.int8, n)
+        mism = int((out != expect).sum()) + mism_inflight
+        mism_all = int(allreduce_sum(mism, world))
+        if mism:
+            log(f"[rank {rank}] VERDICT MISMATCH on {mism} of {n} signatures")
+
+        # roofline (dsm = dominant kernel)
+        ops = workload.ops_per_verify(wl.sizes)
+        clock = eng.clock_mhz() * 1e6
+        peak = clock * info["cu_cnt"] * 64 * 2 / 1e12
+        per_launch = {k: v / max(launches, 1) for k, v in phase_ms.items()}
+        # a launch is one chunk of at most max_chunk signatures: ops per launch
+        # are the step's ops over its chunk count
+        chunks = -(-n // info["max_chunk"])
+        dsm_ops = float(ops["dsm"].sum()) / chunks
+        achieved = dsm_ops / (per_launch["dsm"] * 1e-3) / 1e12 if per_launch["dsm"] > 0 else None
+        path_ms = sum(per_launch.values())
+        path_ops = float(ops["total"].sum()) / chunks
+        path_achieved = path_ops / (path_ms * 1e-3) / 1e12 if path_ms > 0 else None
 
     cpu = c1 = c3 = None
     if rank == 0 and not args.no_cpu_baseline:
@@ -1360,13 +1398,32 @@ def main():
         except Exception as ex:  # reported, never fatal for the device-resident number
             log(f"deployed latency leg failed: {ex!r}")
             lat_dep = {"error": repr(ex)}
-    traffic, traffic_src = pmc_traffic(min(n, info["max_chunk"]))
-    # executed (not algorithmic) instruction rate of the dsm kernel: the
-    # half-size formulation executes fewer operations than the reference's
-    # algorithm counted above, so both are reported
-    valu = pmc_valu_per_sig()
-    sig_launch = min(n, info["max_chunk"])
-    executed = (valu * sig_launch / (per_launch["dsm"] * 1e-3) / 1e12) if valu and per_launch["dsm"] > 0 else None
+    roofline = None
+    if args.full:
+        traffic, traffic_src = pmc_traffic(min(n, info["max_chunk"]))
+        # executed (not algorithmic) instruction rate of the dsm kernel: the
+        # half-size formulation executes fewer operations than the reference's
+        # algorithm counted above, so both are reported
+        valu = pmc_valu_per_sig()
+        sig_launch = min(n, info["max_chunk"])
+        executed = (valu * sig_launch / (per_launch["dsm"] * 1e-3) / 1e12) if valu and per_launch["dsm"] > 0 else None
+        roofline = {"bound": "valu-int32", "kernel": "fd_ed25519_dsm_kernel",
+                    "achieved": achieved, "peak": peak, "unit": "TOPS",
+                    "frac": (achieved / peak) if achieved else None, "traffic": traffic,
+                    "traffic_unit": "bytes per launch (HBM read+write: rocprofv3 2 x FETCH_SIZE (gfx950 16-B/lane "
+                                    "correction) + WRITE_SIZE)",
+                    "traffic_source": traffic_src,
+                    "ops_per_launch": dsm_ops, "launch_ms": per_launch["dsm"],
+                    "executed": {"achieved": executed, "frac": (executed / peak) if executed else None,
+                                 "unit": "TOPS (INT32+INT64 VALU lane-instructions / s)",
+                                 "valu_per_signature": valu, "source": traffic_src,
+                                 "cycles_per_valu_instruction_per_simd": pmc_issue_rate(info["cu_cnt"]),
+                                 "issue_note": "the peak assumes a wave64 instruction every 2 cycles per SIMD; "
+                                               "measured issue costs are 2.5 (VOP2), 4.2-4.4 (VOP3), 5.2 "
+                                               "(32x32->64 mad, 68% of dsm's instructions): DESIGN.md 2.4"},
+                    "path": {"achieved": path_achieved, "frac": (path_achieved / peak) if path_achieved else None,
+                             "ops_per_verify_mean": path_ops * chunks / n, "ms_per_launch": path_ms},
+                    "signatures_per_launch": min(n, info["max_chunk"])}
 
     if rank == 0:
         line = {
@@ -1391,23 +1448,8 @@ def main():
                        "batches_in_flight": inflight,
                        "engine_streams": "one per engine" if one_stream else "two per engine (decode side stream)",
                        "codes": "reference AVX-512 backend"},
-            "roofline": {"bound": "valu-int32", "kernel": "fd_ed25519_dsm_kernel",
-                         "achieved": achieved, "peak": peak, "unit": "TOPS",
-                         "frac": (achieved / peak) if achieved else None, "traffic": traffic,
-                         "traffic_unit": "bytes per launch (HBM read+write: rocprofv3 2 x FETCH_SIZE (gfx950 16-B/lane "
-                                         "correction) + WRITE_SIZE)",
-                         "traffic_source": traffic_src,
-                         "ops_per_launch": dsm_ops, "launch_ms": per_launch["dsm"],
-                         "executed": {"achieved": executed, "frac": (executed / peak) if executed else None,
-                                      "unit": "TOPS (INT32+INT64 VALU lane-instructions / s)",
-                                      "valu_per_signature": valu, "source": traffic_src,
-                                      "cycles_per_valu_instruction_per_simd": pmc_issue_rate(info["cu_cnt"]),
-                                      "issue_note": "the peak assumes a wave64 instruction every 2 cycles per SIMD; "
-                                                    "measured issue costs are 2.5 (VOP2), 4.2-4.4 (VOP3), 5.2 "
-                                                    "(32x32->64 mad, 68% of dsm's instructions): DESIGN.md 2.4"},
-                         "path": {"achieved": path_achieved, "frac": (path_achieved / peak) if path_achieved else None,
-                                  "ops_per_verify_mean": path_ops * chunks / n, "ms_per_launch": path_ms},
-                         "signatures_per_launch": min(n, info["max_chunk"])},
+            "full": args.full,
+            "roofline": roofline,
             "kernel_ms_per_launch": per_launch,
             "kernel_timing": "HIP events around each phase on the engine stream, in a separate pass of the same "
                              "steps on one engine (phases in sequence); in the timed region consecutive steps "
@@ -1426,9 +1468,9 @@ def main():
             "latency_mode_deployed": lat_dep,
             "config_c1": c1,
             "config_c3": c3,
-            "verdicts_match_reference_labels": mism_all == 0,
-            "verdict_mismatches": mism_all,
-            "invalid_fraction": float((expect != 0).mean()),
+            "verdicts_match_reference_labels": (mism_all == 0) if args.full else None,
+            "verdict_mismatches": mism_all if args.full else None,
+            "invalid_fraction": float((expect != 0).mean()) if args.full else None,
             "gen_seconds": gen_s,
         }
         print(json.dumps(line), flush=True)

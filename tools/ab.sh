@@ -10,7 +10,7 @@ for rep in $(seq $REPS); do
     [ "$spec" != "$name" ] && envs=$(echo ${spec#*,} | tr ',' ' ')
     lib=$R/build/variants/$name/libfd_ed25519_hip.so
     [ "$name" = "main" ] && lib=$R/firedancer_amd/_lib/libfd_ed25519_hip.so
-    out=$(env FD_ED25519_HIP_LIB=$lib $envs timeout -k 10 200 python3 $R/bench.py --steps 10 --no-cpu-baseline \
+    out=$(env FD_ED25519_HIP_LIB=$lib $envs timeout -k 10 200 python3 $R/bench.py --full --steps 10 --no-cpu-baseline \
           --latency-txns 0 --deployed-txns 0 --host-reps 0 --c4-signatures 0 2>/dev/null)
     rc=$?
     # rc 1 with a JSON line = verdict mismatch (expected for timing-only variants); anything else is fatal

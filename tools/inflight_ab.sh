@@ -3,7 +3,7 @@
 # usage: tools/inflight_ab.sh REPS STEPS "SPEC" ...   SPEC = bench.py arguments
 R=${GRAFT_REPO_ROOT:-$(pwd)}
 REPS=$1; STEPS=$2; shift 2
-B="python3 $R/bench.py --steps $STEPS --no-cpu-baseline --latency-txns 0 --host-reps 0"
+B="python3 $R/bench.py --full --steps $STEPS --no-cpu-baseline --latency-txns 0 --host-reps 0"
 for rep in $(seq $REPS); do
   for spec in "$@"; do
     out=$(timeout -k 10 200 $B $spec 2>/dev/null) || { echo "$spec FAILED"; exit 1; }
