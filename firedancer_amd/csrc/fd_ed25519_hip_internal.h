@@ -188,58 +188,124 @@ int fd_ed25519_hip_launch_phase( fd_ed25519_verify_params_t const * p, int phase
    launches whose points and split scalars all came from the host */
 int fd_ed25519_hip_launch_dsm16s( fd_ed25519_verify_params_t const * p, int waves, void * stream );
 
-/* Host scalars (host/fd_ed25519_hip_hsrec.cc, host/fd_ed25519_hip_engine.c):
-   a launch of a few signatures whose k, S < L and half-size pair the
-   calling thread computes while the device decompresses A and R.
+/* Host scalars (host/fd_ed25519_hip_hs.c, hsrec.cc, hsdec.cc): a launch of
+   a few signatures whose k, S < L and half-size pair the calling thread
+   computes while the device decompresses A and R -- or, for the fewest,
+   whose A and R the calling thread decompresses too, dsm16 launched ahead
+   of that work and waiting on the go word (params.go).
    hsrec: 1 and the 32-word record (k[8], hs[19], sflag, hflag), or 0 when
    k has no half-size pair within dbits (the launch then takes the device's
-   own path).  hs_decode: prep16's decode blocks; hs_dsm: dsm16 with
-   sflag [cap], hflag [cap], hs [19][cap] read in place (cap = the engine's
-   max_chunk).  The engine's dsm16 form must take n (n <= its r16 bound).
-   Host decompressions (host/fd_ed25519_hip_hsdec.cc) for the fewest
-   signatures: hsdec_n writes each point's 20 limbs and flags as the decode
-   blocks would, and hs_dsm then reads pts [2][20][cap] and pflag [2][cap]
-   in place too (pts NULL: the decode blocks' arrays on the device).  go:
-   NULL, or the page-locked word dsm16 waits on (params.go): the caller
-   launches first, writes the block, then stores FD_ED25519_GO_RUN (or
-   FD_ED25519_GO_CANCEL) -- on every path, or the kernel spins to its bound. */
-#ifdef __cplusplus
-extern "C" {
-#endif
-struct fd_ed25519_hip_engine;
-int fd_ed25519_hip_private_hsrec( unsigned char const sig[ 64 ], unsigned char const pub[ 32 ],
-                                  unsigned char const * msg, unsigned long msg_sz, int dbits, uint32_t rec[ 32 ] );
-int fd_ed25519_hip_private_half_dbits( struct fd_ed25519_hip_engine const * e );
-int fd_ed25519_hip_private_codes_portable( struct fd_ed25519_hip_engine const * e );
-int fd_ed25519_hip_private_hs_decode( struct fd_ed25519_hip_engine * e, unsigned long n, unsigned char const * sigs,
-                                      unsigned char const * pubs, signed char * out, void * stream );
-int fd_ed25519_hip_private_hs_dsm( struct fd_ed25519_hip_engine * e, unsigned long n, unsigned char const * sigs,
-                                   unsigned char const * pubs, signed char * out, unsigned char const * sflag,
-                                   unsigned char const * hflag, unsigned int const * hs, int const * pts,
-                                   unsigned char const * pflag, unsigned int const * go, void * stream );
-void fd_ed25519_hip_private_hsdec_n( unsigned char const * const * enc, unsigned long n, int avx_rule, int32_t * pt,
-                                     unsigned char * flags );
-/* The split forms (dsm16s<S>, S = 4 or 8 waves) for host-decoded
+   own path).  hsdec_n writes each point's 20 limbs and flags as the decode
+   blocks would.
+   The split forms (dsm16s<S>, S = 4 or 8 waves) for host-decoded
    launches: hssplit turns one signature's record into the split scalars
    and s' chunks (hq: 24 rows of stride cap, layout at the function), and
    hsdec3_n also returns each point doubled step, 2 step, .. nx step times
    (S = 4: nx 1, step 66; S = 8: nx 3, step 33) in extended coordinates
    (40 limbs) for pts rows 2i + side of 40 limbs (row 0 A, 1 R -- affine,
-   the first 20 -- 2 A_1, 3 R_1, ..); hs_dsms launches dsm16s<waves> on them
-   once want_dsms has made (or found) the engine's tables for that form. */
+   the first 20 -- 2 A_1, 3 R_1, ..); want_dsms makes (or finds) the
+   engine's tables for that form. */
+struct fd_ed25519_hip_engine;
+int fd_ed25519_hip_private_hsrec( unsigned char const sig[ 64 ], unsigned char const pub[ 32 ],
+                                  unsigned char const * msg, unsigned long msg_sz, int dbits, uint32_t rec[ 32 ] );
+int fd_ed25519_hip_private_half_dbits( struct fd_ed25519_hip_engine const * e );
+int fd_ed25519_hip_private_codes_portable( struct fd_ed25519_hip_engine const * e );
+void fd_ed25519_hip_private_hsdec_n( unsigned char const * const * enc, unsigned long n, int avx_rule, int32_t * pt,
+                                     unsigned char * flags );
 void fd_ed25519_hip_private_hssplit( uint32_t const rec[ 32 ], int waves, uint32_t * hq, unsigned long cap,
                                      unsigned long j );
 void fd_ed25519_hip_private_hsdec3_n( unsigned char const * const * enc, unsigned long n, int avx_rule, int32_t * pt,
                                       int32_t * ptx, int nx, int step, unsigned char * flags );
-int fd_ed25519_hip_private_hs_dsms( struct fd_ed25519_hip_engine * e, int waves, unsigned long n,
-                                    unsigned char const * sigs, unsigned char const * pubs, signed char * out,
-                                    unsigned char const * sflag, unsigned char const * hflag, unsigned int const * hq,
-                                    int const * pts, unsigned char const * pflag, unsigned int const * go,
-                                    void * stream );
 int fd_ed25519_hip_private_want_dsms( struct fd_ed25519_hip_engine * e, int waves );
-#ifdef __cplusplus
-}
-#endif
+
+/* The host-scalar block (host/fd_ed25519_hip_hs.c): what the calling thread
+   writes and dsm16 / dsm16s read in place, every array [row][stride] (signature
+   j of the launch at column j) and starting 16-byte aligned in a 16-byte
+   aligned block:
+     sflag [stride]         u8   S < L
+     hflag [stride]         u8   bit0 d < 0
+     hs    [24][stride]     u32  dsm16: rows 0..18, hsrec's rec[8..26];
+                                 dsm16s: 24 rows, hssplit's
+     pts   [8][40][stride]  i32  dsm16: rows of 20 limbs (A, R: x, y);
+                                 dsm16s: rows of 40 limbs (A, R, A_1, R_1, ..)
+     pflag [2][stride]      u8   A, R: hsdec3_n's flags
+     go    16 bytes              word 0: params.go
+   pts, pflag and go exist only in a host-decoded block, whose stride is
+   FD_ED25519_HS_STRIDE; a block whose points the device decodes has the
+   work arrays' stride (the engine's max_chunk) and ends after hs row 18
+   (the split forms are host-decoded). */
+#define FD_ED25519_HS_ALIGN16( x ) ( ( (x) + 15UL ) & ~15UL )
+#define FD_ED25519_HS_O_SFLAG( s ) 0UL
+#define FD_ED25519_HS_O_HFLAG( s ) FD_ED25519_HS_ALIGN16( s )
+#define FD_ED25519_HS_O_HS( s )    ( 2UL*FD_ED25519_HS_ALIGN16( s ) )
+#define FD_ED25519_HS_O_PTS( s )   ( FD_ED25519_HS_O_HS( s ) + 24UL*4UL*(s) )
+#define FD_ED25519_HS_O_PFLAG( s ) ( FD_ED25519_HS_O_PTS( s ) + 8UL*40UL*4UL*(s) )
+#define FD_ED25519_HS_O_GO( s )    FD_ED25519_HS_ALIGN16( FD_ED25519_HS_O_PFLAG( s ) + 2UL*(s) )
+/* host-decoded launches have at most this many signatures (hs_points'
+   arrays; the drop-in's and the pipe's setters clamp to it) */
+#define FD_ED25519_HS_DECODE_MAX 4UL
+
+/* One host-scalar launch.  hs_init describes the block and the launch
+   (host only: nothing of the GPU is touched, so the fill steps also run on
+   ordinary memory); hs_begin attaches the device side and launches; the
+   caller then walks its own inputs with hs_scalars (and hands hs_points
+   the encodings); hs_end, exactly once after a hs_begin that returned 0,
+   finishes the launch. */
+typedef struct {
+  unsigned char * host;     /* the block, where the calling thread writes it */
+  unsigned long   stride;
+  int             decode;   /* the calling thread decodes A and R (pts, pflag, go) */
+  unsigned long   n;        /* signatures, columns 0..n-1 */
+  int             split;    /* 0: dsm16; 4, 8: dsm16s<split> (decode only) */
+  int             avx_rule; /* hsdec3_n's: the engine has no FD_ED25519_HIP_FLAG_CODES_PORTABLE */
+  /* set by hs_begin: the block, the signatures, the keys and the codes as
+     the device sees them, and where the launches go */
+  struct fd_ed25519_hip_engine * eng;
+  unsigned char const * dev;
+  unsigned char const * sigs;
+  unsigned char const * pubs;
+  signed char *         out;
+  void *                stream;
+} fd_ed25519_hip_hs_t;
+/* a descriptor fits in this many bytes (tests hold one in a plain buffer) */
+#define FD_ED25519_HS_DESC_MAX 128
+
+/* bytes of a block of that stride */
+unsigned long fd_ed25519_hip_private_hs_bytes( unsigned long stride, int decode );
+void fd_ed25519_hip_private_hs_init( fd_ed25519_hip_hs_t * b, void * host, unsigned long stride, int decode,
+                                     unsigned long n, int split, int avx_rule );
+/* host-decoded: zeroes the go word, then launches dsm16 (or dsm16s<split>)
+   waiting on it, ahead of the caller's arithmetic; else launches prep16's
+   decode blocks.  Not 0 (a FD_ED25519_HIP_ERR_*): nothing was launched and
+   no hs_end follows. */
+int fd_ed25519_hip_private_hs_begin( fd_ed25519_hip_hs_t * b, struct fd_ed25519_hip_engine * e,
+                                     unsigned char const * dev, unsigned char const * sigs,
+                                     unsigned char const * pubs, signed char * out, void * stream );
+/* signature j's scalars and flags into the block.  0: k has no half-size
+   pair within dbits, nothing was written and the launch ends with
+   hs_end( b, 0 ) */
+int fd_ed25519_hip_private_hs_scalars( fd_ed25519_hip_hs_t * b, unsigned long j, unsigned char const sig[ 64 ],
+                                       unsigned char const pub[ 32 ], unsigned char const * msg, unsigned long msg_sz,
+                                       int dbits );
+/* host-decoded only: enc[2j] signature j's A, enc[2j+1] its R (2n
+   encodings); the points (doubled too, for a split form) and their flags
+   into the block */
+void fd_ed25519_hip_private_hs_points( fd_ed25519_hip_hs_t * b, unsigned char const * const * enc );
+/* host-decoded: the release store of FD_ED25519_GO_RUN (run not 0) or
+   FD_ED25519_GO_CANCEL, after every write of the block; else dsm16's
+   launch when run is not 0, nothing when it is 0 */
+int fd_ed25519_hip_private_hs_end( fd_ed25519_hip_hs_t * b, int run );
+/* the engine's side of hs_begin / hs_end (host/fd_ed25519_hip_engine.c):
+   prep16's decode blocks (dsm 0), or dsm16 / dsm16s<b->split> reading b's
+   block in place (a host-decoded one: waiting on its go word).  The
+   engine's dsm16 form must take n (n <= its r16 bound). */
+int fd_ed25519_hip_private_hs_launch( fd_ed25519_hip_hs_t const * b, int dsm );
+/* fd_ed25519_verify_batch_single_msg's rule on the host, for a
+   transaction's codes[first .. first+cnt) (the device's is
+   fd_ed25519_hip_launch_txn_combine below): cnt==0 or cnt>16 ERR_SIG; else
+   the first error other than ERR_MSG in signature order, else ERR_MSG if
+   any signature had it, else SUCCESS */
+int fd_ed25519_hip_private_hs_combine( signed char const * codes, unsigned long first, unsigned long cnt );
 int fd_ed25519_hip_verify_occupancy( int * blocks_per_cu );
 /* lane-table bytes per dsm wave as compiled into the kernels (the host
    sizes the atab scratch from this, never from its own copy of the macro) */

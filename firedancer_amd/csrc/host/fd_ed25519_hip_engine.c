@@ -752,12 +752,11 @@ fd_ed25519_hip_verify_dev( fd_ed25519_hip_engine_t * e,
   return verify_common( e, n, msgs, msg_off, msg_sz, NULL, sigs, pubs, out, stream );
 }
 
-/* The drop-in's host-scalar launches (dropin_run, a few signatures): the
-   decompressions first (prep16's decode blocks only), and the group
-   equation (dsm16) once the calling thread has written each signature's
-   scalars (fd_ed25519_hip_private_hsrec) into page-locked memory the device
-   reads in place -- sflag [cap], hflag [cap] and hs [19][cap], the work
-   arrays' layout.  The caller computes while the decompressions run. */
+/* A host-scalar launch (host/fd_ed25519_hip_hs.c, a few signatures of the
+   drop-in or of a pipe's batch): the calling thread writes each
+   signature's scalars -- and, host-decoded, its points -- into a
+   page-locked block the device reads in place (the layout in
+   fd_ed25519_hip_internal.h), everything else being lane 0's work arrays. */
 static int
 hs_params( fd_ed25519_hip_engine_t * e, fd_ed25519_verify_params_t * p, unsigned long n, unsigned char const * sigs,
            unsigned char const * pubs, signed char * out ) {
@@ -785,53 +784,38 @@ fd_ed25519_hip_private_codes_portable( fd_ed25519_hip_engine_t const * e ) {
 }
 
 int
-fd_ed25519_hip_private_hs_decode( fd_ed25519_hip_engine_t * e, unsigned long n, unsigned char const * sigs,
-                                  unsigned char const * pubs, signed char * out, void * stream ) {
+fd_ed25519_hip_private_hs_launch( fd_ed25519_hip_hs_t const * b, int dsm ) {
+  fd_ed25519_hip_engine_t * e = b->eng;
   fd_ed25519_verify_params_t p;
-  int err = hs_params( e, &p, n, sigs, pubs, out );
+  int err = hs_params( e, &p, b->n, b->sigs, b->pubs, b->out );
   if( err ) return err;
-  HIPCHK( hipSetDevice( e->device ), "hipSetDevice" );
-  err = fd_ed25519_hip_launch_phase( &p, FD_ED25519_PHASE_HASH, e->dsm_grid, stream ? (hipStream_t)stream : e->stream );
-  if( err ) return hip_fail( (hipError_t)err, "verify launch" );
-  return FD_ED25519_HIP_OK;
-}
-
-int
-fd_ed25519_hip_private_hs_dsm( fd_ed25519_hip_engine_t * e, unsigned long n, unsigned char const * sigs,
-                               unsigned char const * pubs, signed char * out, unsigned char const * sflag,
-                               unsigned char const * hflag, unsigned int const * hs, int const * pts,
-                               unsigned char const * pflag, unsigned int const * go, void * stream ) {
-  fd_ed25519_verify_params_t p;
-  int err = hs_params( e, &p, n, sigs, pubs, out );
-  if( err ) return err;
-  if( !sflag || !hflag || !hs || !pts!=!pflag ) return FD_ED25519_HIP_ERR_INVAL;
-  p.sflag = (uint8_t *)sflag; p.hflag = (uint8_t *)hflag; p.hs = (uint32_t *)hs;
-  if( pts ) {   /* every array the caller's: its small stride */
-    if( n>FD_ED25519_HS_STRIDE ) return FD_ED25519_HIP_ERR_INVAL;
-    p.pts = (int32_t *)pts; p.pflag = (uint8_t *)pflag; p.cap = FD_ED25519_HS_STRIDE;
+  hipStream_t st = b->stream ? (hipStream_t)b->stream : e->stream;
+  if( !dsm ) {
+    HIPCHK( hipSetDevice( e->device ), "hipSetDevice" );
+    err = fd_ed25519_hip_launch_phase( &p, FD_ED25519_PHASE_HASH, e->dsm_grid, st );
+  } else {
+    int waves = b->split;
+    /* a device-decoded block has the work arrays' stride (p.cap, which the
+       device's pts / pflag have too) */
+    if( !b->dev || b->stride!=( b->decode ? FD_ED25519_HS_STRIDE : e->max_chunk ) ) return FD_ED25519_HIP_ERR_INVAL;
+    if( waves && ( (waves!=4 && waves!=8) || !b->decode || !e->btabs[ split_set( waves ) ][0] ) )
+      return FD_ED25519_HIP_ERR_INVAL;
+    uint8_t * d = (uint8_t *)b->dev;
+    p.sflag = d + FD_ED25519_HS_O_SFLAG( b->stride ); p.hflag = d + FD_ED25519_HS_O_HFLAG( b->stride );
+    p.hs = (uint32_t *)( d + FD_ED25519_HS_O_HS( b->stride ) );
+    if( b->decode ) {   /* every array the caller's: its small stride */
+      if( b->n>FD_ED25519_HS_STRIDE ) return FD_ED25519_HIP_ERR_INVAL;
+      p.pts = (int32_t *)( d + FD_ED25519_HS_O_PTS( b->stride ) ); p.pflag = d + FD_ED25519_HS_O_PFLAG( b->stride );
+      p.go = (uint32_t const *)( d + FD_ED25519_HS_O_GO( b->stride ) );
+      p.cap = FD_ED25519_HS_STRIDE;
+    }
+    if( waves ) {
+      for( int q=0; q<8; q++ ) p.btabq[q] = e->btabs[ split_set( waves ) ][q];
+      err = fd_ed25519_hip_launch_dsm16s( &p, waves, st );
+    } else {
+      err = fd_ed25519_hip_launch_phase( &p, FD_ED25519_PHASE_DSM, e->dsm_grid, st );
+    }
   }
-  p.go = (uint32_t const *)go;
-  err = fd_ed25519_hip_launch_phase( &p, FD_ED25519_PHASE_DSM, e->dsm_grid, stream ? (hipStream_t)stream : e->stream );
-  if( err ) return hip_fail( (hipError_t)err, "verify launch" );
-  return FD_ED25519_HIP_OK;
-}
-
-int
-fd_ed25519_hip_private_hs_dsms( fd_ed25519_hip_engine_t * e, int waves, unsigned long n, unsigned char const * sigs,
-                                unsigned char const * pubs, signed char * out, unsigned char const * sflag,
-                                unsigned char const * hflag, unsigned int const * hq, int const * pts,
-                                unsigned char const * pflag, unsigned int const * go, void * stream ) {
-  fd_ed25519_verify_params_t p;
-  int err = hs_params( e, &p, n, sigs, pubs, out );
-  if( err ) return err;
-  if( (waves!=4 && waves!=8) || !sflag || !hflag || !hq || !pts || !pflag || !e->btabs[ split_set( waves ) ][0] )
-    return FD_ED25519_HIP_ERR_INVAL;
-  if( n>FD_ED25519_HS_STRIDE ) return FD_ED25519_HIP_ERR_INVAL;
-  p.sflag = (uint8_t *)sflag; p.hflag = (uint8_t *)hflag; p.hs = (uint32_t *)hq;
-  p.pts = (int32_t *)pts; p.pflag = (uint8_t *)pflag; p.cap = FD_ED25519_HS_STRIDE;   /* every array the caller's */
-  p.go = (uint32_t const *)go;
-  for( int q=0; q<8; q++ ) p.btabq[q] = e->btabs[ split_set( waves ) ][q];
-  err = fd_ed25519_hip_launch_dsm16s( &p, waves, stream ? (hipStream_t)stream : e->stream );
   if( err ) return hip_fail( (hipError_t)err, "verify launch" );
   return FD_ED25519_HIP_OK;
 }
@@ -1288,7 +1272,6 @@ fd_ed25519_hip_dropin_set_host_scalars_dbits( int dbits ) {
 #ifndef DROPIN_HD_MAX
 #define DROPIN_HD_MAX 2UL
 #endif
-#define DROPIN_HD_CAP 4UL   /* the hook's bound: the host arrays below */
 static unsigned long dropin_hd_max = DROPIN_HD_MAX;
 
 /* host-decoded drop-in launches take the split form of this many waves
@@ -1310,7 +1293,7 @@ fd_ed25519_hip_dropin_set_split_waves( int waves ) {
 
 void
 fd_ed25519_hip_dropin_set_host_decode( unsigned long max_sigs ) {
-  dropin_hd_max = max_sigs>DROPIN_HD_CAP ? DROPIN_HD_CAP : max_sigs;
+  dropin_hd_max = max_sigs>FD_ED25519_HS_DECODE_MAX ? FD_ED25519_HS_DECODE_MAX : max_sigs;
 }
 
 static pthread_once_t  dropin_once = PTHREAD_ONCE_INIT;
@@ -1493,14 +1476,9 @@ dropin_run( int k, dropin_req_t * list, unsigned long n ) {
   /* the host arrays' stride: the work arrays' when the device decodes
      (its pts / pflag), a small one when every array is the caller's */
   uint64_t cap_hs = hdmode ? FD_ED25519_HS_STRIDE : e->max_chunk;
-  uint64_t o_hsf = DROPIN_ALIGN16( need ), o_hhf = DROPIN_ALIGN16( o_hsf + cap_hs ), o_hs = DROPIN_ALIGN16( o_hhf + cap_hs );
-  /* hs: 19 rows (dsm16) or 24 (dsm16s's split scalars); pts: A, R and,
-     for dsm16s, the doubled points (up to 8 rows of 40 limbs: dsm16s reads
-     rows of 40, dsm16 of 20) */
+  uint64_t o_hsb  = DROPIN_ALIGN16( need );   /* the host-scalar block (fd_ed25519_hip_internal.h) */
   int split = hdmode && dropin_split>2 && fd_ed25519_hip_private_want_dsms( e, dropin_split ) ? dropin_split : 0;
-  uint64_t o_pts = DROPIN_ALIGN16( o_hs + 24UL*4UL*cap_hs ), o_pfl = DROPIN_ALIGN16( o_pts + 8UL*40UL*4UL*cap_hs );
-  uint64_t o_go  = DROPIN_ALIGN16( o_pfl + 2UL*cap_hs );
-  if( hsmode ) need = hdmode ? o_go + 16UL : o_hs + 19UL*4UL*cap_hs;
+  if( hsmode ) need = o_hsb + fd_ed25519_hip_private_hs_bytes( cap_hs, hdmode );
   if( need>dq.blk_cap[k] ) {
     uint64_t cap = dq.blk_cap[k] ? dq.blk_cap[k] : (1UL<<20);
     while( cap<need ) cap *= 2UL;
@@ -1573,78 +1551,26 @@ dropin_run( int k, dropin_req_t * list, unsigned long n ) {
        thread's scalars and decompressions while it is dispatched (a
        signature without a half-size pair, ~1e-6, sends the launch down the
        device's own path instead) */
-    volatile uint32_t * go = (volatile uint32_t *)(h + o_go);
-    if( !hdmode ) {
-      err = fd_ed25519_hip_private_hs_decode( e, nsig, src + o_sig, src + o_pub, (signed char *)(src + o_out), st );
-      if( err ) { hipStreamSynchronize( st ); return err; }
-    } else {
-      /* dsm16 goes first and waits on the go word (params.go), so its
-         dispatch overlaps this thread's scalars and decompressions; from
-         here every path stores RUN or CANCEL */
-      *go = 0U;
-      if( split )
-        err = fd_ed25519_hip_private_hs_dsms( e, split, nsig, src + o_sig, src + o_pub, (signed char *)(src + o_out),
-                                              src + o_hsf, src + o_hhf, (unsigned int const *)(src + o_hs),
-                                              (int const *)(src + o_pts), src + o_pfl,
-                                              (unsigned int const *)(src + o_go), st );
-      else
-        err = fd_ed25519_hip_private_hs_dsm( e, nsig, src + o_sig, src + o_pub, (signed char *)(src + o_out),
-                                             src + o_hsf, src + o_hhf, (unsigned int const *)(src + o_hs),
-                                             (int const *)(src + o_pts), src + o_pfl,
-                                             (unsigned int const *)(src + o_go), st );
-      if( err ) { hipStreamSynchronize( st ); return err; }
-    }
-    uint8_t *  hsf = (uint8_t *)(h + o_hsf);
-    uint8_t *  hhf = (uint8_t *)(h + o_hhf);
-    uint32_t * hs  = (uint32_t *)(h + o_hs);
+    fd_ed25519_hip_hs_t hb;
+    fd_ed25519_hip_private_hs_init( &hb, h + o_hsb, cap_hs, hdmode, nsig, split,
+                                    !(e->flags & FD_ED25519_HIP_FLAG_CODES_PORTABLE) );
+    err = fd_ed25519_hip_private_hs_begin( &hb, e, src + o_hsb, src + o_sig, src + o_pub, (signed char *)(src + o_out), st );
+    if( err ) { hipStreamSynchronize( st ); return err; }
     int all = 1;
     int dbits = dropin_hs_dbits ? dropin_hs_dbits : engine_half_dbits( e );
+    /* signature j (the requests' signatures in order): A at enc[2j], R at enc[2j+1] */
+    unsigned char const * enc[ 2UL*FD_ED25519_HS_DECODE_MAX ];
     t = 0UL;
     for( dropin_req_t * r=list; r && all; r=r->next, t++ ) {
       for( uint32_t i=0U; i<r->cnt && all; i++ ) {   /* a batch_single_msg request: its signatures over one message */
-        uint32_t rec[ 32 ];
-        all = fd_ed25519_hip_private_hsrec( r->sigs + 64UL*i, r->pubs + 32UL*i, r->msg, r->msg_sz, dbits, rec );
-        if( !all ) break;
         uint64_t j = tf[ t ] + i;
-        if( split ) fd_ed25519_hip_private_hssplit( rec, split, hs, cap_hs, j );
-        else for( int w=0; w<19; w++ ) hs[ (uint64_t)w*cap_hs + j ] = rec[ 8 + w ];
-        hsf[ j ] = (uint8_t)rec[ 27 ];
-        hhf[ j ] = (uint8_t)rec[ 28 ];
+        all = fd_ed25519_hip_private_hs_scalars( &hb, j, r->sigs + 64UL*i, r->pubs + 32UL*i, r->msg, r->msg_sz, dbits );
+        if( hdmode ) { enc[ 2UL*j ] = r->pubs + 32UL*i; enc[ 2UL*j + 1UL ] = r->sigs + 64UL*i; }
       }
     }
-    if( all && hdmode ) {   /* A and R of each signature, side by side (and doubled, for dsm16s) */
-      unsigned char const * enc[ 2UL*DROPIN_HD_CAP ];
-      int32_t       pt[ 2UL*DROPIN_HD_CAP ][ 20 ], ptx[ 2UL*DROPIN_HD_CAP*3UL ][ 40 ];
-      unsigned char fl[ 2UL*DROPIN_HD_CAP ];
-      int nx = split ? split/2 - 1 : 0, step = split==4 ? 66 : 33;
-      /* signature j (the requests' signatures in order) at enc[2j], enc[2j+1] */
-      t = 0UL;
-      for( dropin_req_t * r=list; r; r=r->next, t++ )
-        for( uint32_t i=0U; i<r->cnt; i++ ) {
-          enc[ 2UL*( tf[ t ] + i ) ] = r->pubs + 32UL*i; enc[ 2UL*( tf[ t ] + i ) + 1UL ] = r->sigs + 64UL*i;
-        }
-      fd_ed25519_hip_private_hsdec3_n( enc, 2UL*nsig, !(e->flags & FD_ED25519_HIP_FLAG_CODES_PORTABLE), &pt[0][0],
-                                       split ? &ptx[0][0] : NULL, nx, step, fl );
-      int32_t * pts = (int32_t *)(h + o_pts);
-      uint8_t * pfl = (uint8_t *)(h + o_pfl);
-      uint64_t rs = split ? 40UL : 20UL;   /* the row stride in limbs: dsm16s's, dsm16's */
-      for( uint64_t j=0UL; j<nsig; j++ ) {
-        for( uint64_t side=0UL; side<2UL; side++ ) {   /* rows 2i + side: A, R, A_1, R_1, .. */
-          uint64_t pi = 2UL*j + side;
-          for( uint64_t l=0UL; l<20UL; l++ ) pts[ ( side*rs + l )*cap_hs + j ] = pt[ pi ][ l ];
-          for( int m=1; m<=nx; m++ )
-            for( uint64_t l=0UL; l<40UL; l++ )
-              pts[ ( ( 2UL*(uint64_t)m + side )*40UL + l )*cap_hs + j ] = ptx[ pi*(uint64_t)nx + (uint64_t)(m-1) ][ l ];
-          pfl[ side*cap_hs + j ] = fl[ pi ];
-        }
-      }
-    }
-    if( hdmode ) __atomic_store_n( go, all ? FD_ED25519_GO_RUN : FD_ED25519_GO_CANCEL, __ATOMIC_RELEASE );
-    if( all && !hdmode ) {
-      err = fd_ed25519_hip_private_hs_dsm( e, nsig, src + o_sig, src + o_pub, (signed char *)(src + o_out),
-                                           src + o_hsf, src + o_hhf, (unsigned int const *)(src + o_hs), NULL, NULL,
-                                           NULL, st );
-    } else if( !all ) {   /* the device path from the digests (the messages were not staged) */
+    if( all && hdmode ) fd_ed25519_hip_private_hs_points( &hb, enc );
+    err = fd_ed25519_hip_private_hs_end( &hb, all );
+    if( !err && !all ) {   /* the device path from the digests (the messages were not staged) */
       t = 0UL;
       for( dropin_req_t * r=list; r; r=r->next, t++ )
         for( uint32_t i=0U; i<r->cnt; i++ )
@@ -1706,21 +1632,11 @@ dropin_run( int k, dropin_req_t * list, unsigned long n ) {
   signed char const * codes = (signed char const *)(h + o_out);
   signed char const * tcode = (signed char const *)(h + o_tout);
   if( multi && direct ) {
-    /* batch_single_msg's rule per request (fd_ed25519_user.c:231-309, the
-       device's fd_ed25519_txn_combine_kernel): the first error other than
-       ERR_MSG in signature order, else ERR_MSG if any signature had it,
-       else SUCCESS (1..16 signatures: the guard ran before submit) */
+    /* batch_single_msg's rule per request (1..16 signatures: the guard ran
+       before submit) */
     t = 0UL;
-    for( dropin_req_t * r=list; r; r=r->next, t++ ) {
-      int code = FD_ED25519_SUCCESS, msg_fail = 0;
-      for( uint32_t i=0U; i<r->cnt; i++ ) {
-        int c = codes[ tf[ t ] + i ];
-        if( c==FD_ED25519_ERR_MSG ) msg_fail = 1;
-        else if( c!=FD_ED25519_SUCCESS ) { code = c; break; }
-      }
-      if( code==FD_ED25519_SUCCESS && msg_fail ) code = FD_ED25519_ERR_MSG;
-      ((signed char *)(h + o_tout))[ t ] = (signed char)code;
-    }
+    for( dropin_req_t * r=list; r; r=r->next, t++ )
+      ((signed char *)(h + o_tout))[ t ] = (signed char)fd_ed25519_hip_private_hs_combine( codes, tf[ t ], r->cnt );
   }
   t = 0UL;
   for( dropin_req_t * r=list; r; r=r->next, t++ )

@@ -1,7 +1,7 @@
 /* fd_ed25519_hip_hsdec.cc -- a point decompression on the calling thread,
    for the launches of a few signatures that also take their scalars from it
-   (host/fd_ed25519_hip_hsrec.cc; host/fd_ed25519_hip_engine.c dropin_run,
-   host/fd_ed25519_hip_tile.c pipe_submit_hs).
+   (host/fd_ed25519_hip_hsrec.cc; host/fd_ed25519_hip_hs.c's sequence, for
+   the drop-in and the verify tile's pipe).
 
    Why on the host: a decompression is one chain of ~265 dependent field
    operations (x = u v^3 (u v^7)^((p-5)/8)).  A row of 16 lanes runs it in

@@ -1,6 +1,6 @@
 /* fd_ed25519_hip_hsrec.cc -- the scalar part of one signature's verify on
-   the calling thread, for the drop-in's direct launches of a few
-   signatures (host/fd_ed25519_hip_engine.c, dropin_run).
+   the calling thread, for the drop-in's and the pipe's launches of a few
+   signatures (host/fd_ed25519_hip_hs.c).
 
    What prep16's hash blocks compute on the device (fd_ed25519_kernels.hip:
    hash16_block -> hash_finish, scalar_one), here in host C++:

@@ -1,11 +1,14 @@
-/* fd_ed25519_hip_sha512.c -- SHA-512 on the host, for the one case the
-   device path cannot take: the drop-in verify of a message whose size does
+/* fd_ed25519_hip_sha512.c -- SHA-512 on the host, for the two cases where
+   the calling thread hashes R || A || M (fd_ed25519_user.c:199-205's
+   challenge) itself.  Every host-scalar launch (a few signatures of the
+   drop-in or of a pipe's batch, host/fd_ed25519_hip_hsrec.cc): the scalars
+   start from this digest, and a launch whose k has no half-size pair hands
+   it to the device.  And the drop-in verify of a message whose size does
    not fit the device path's 32-bit message sizes (4 GiB and more; the
-   reference takes any ulong size, src/ballet/ed25519/fd_ed25519.h:96-101).
-   The caller's thread hashes R || A || M (fd_ed25519_user.c:199-205's
-   challenge) and the device takes the digest from there
-   (fd_ed25519_hip_verify_digests_dev): reduction mod L, decompression and
-   the group equation stay on the GPU.
+   reference takes any ulong size, src/ballet/ed25519/fd_ed25519.h:96-101):
+   the device takes the digest from there
+   (fd_ed25519_hip_verify_digests_dev), reduction mod L, decompression and
+   the group equation staying on the GPU.
 
    FIPS 180-4 SHA-512, the same function as src/ballet/sha512/fd_sha512.c's
    core (fd_sha512_core_ref) -- written here from the standard, plain C,

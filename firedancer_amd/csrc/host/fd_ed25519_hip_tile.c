@@ -81,7 +81,10 @@ fd_ed25519_hip_abi_check( unsigned version, unsigned long slot_sz, unsigned long
 
 
 #ifdef FD_ED25519_HIP_AB_SERVICE_PROFILE
-/* A/B build only: host cycles inside each part of a batch submit */
+/* A/B build only: host cycles inside each part of a batch submit
+   (pf_sub_launch, for a host-scalar batch: the module's launching steps,
+   fd_ed25519_hip_private_hs_begin and hs_end, whose go-word stores it then
+   counts too) */
 static __thread unsigned long long pf_sub_h2d, pf_sub_launch, pf_sub_d2h, pf_sub_n, pf_sub_wait;
 #define PF_SUB( acc, stmt ) do { unsigned long long c_ = __rdtsc(); stmt; acc += __rdtsc() - c_; } while(0)
 #else
@@ -188,9 +191,9 @@ typedef struct {
   unsigned char *           h_in_dev;       /* h_in's device-visible address   */
   unsigned char *           h_outb_dev;     /* h_outb's device-visible address */
   /* host-scalar batches (at most PIPE_HS_MAX signatures, pipe_submit_hs):
-     sflag [sig_cap], hflag [sig_cap], hs [19][sig_cap] written by the
-     submitting thread and read in place by dsm16; the transactions' codes
-     combined on the host when the batch completes */
+     the block the submitting thread writes and dsm16 reads in place
+     (fd_ed25519_hip_internal.h), at either of its strides; the
+     transactions' codes combined on the host when the batch completes */
   unsigned char *           h_hs;
   unsigned char *           h_hs_dev;
   int                       host_combine;
@@ -224,7 +227,6 @@ fd_ed25519_hip_pipe_set_host_scalars( unsigned long max_sigs ) {
 #ifndef PIPE_HD_MAX
 #define PIPE_HD_MAX 4UL
 #endif
-#define PIPE_HD_CAP 4UL
 static unsigned long pipe_hd_max = PIPE_HD_MAX;
 
 /* ... in a split form's four or eight waves (dsm16s) or dsm16's two (2,
@@ -250,18 +252,8 @@ fd_ed25519_hip_pipe_set_split_waves( int waves ) {
 
 void
 fd_ed25519_hip_pipe_set_host_decode( unsigned long max_sigs ) {
-  pipe_hd_max = max_sigs>PIPE_HD_CAP ? PIPE_HD_CAP : max_sigs;
+  pipe_hd_max = max_sigs>FD_ED25519_HS_DECODE_MAX ? FD_ED25519_HS_DECODE_MAX : max_sigs;
 }
-
-/* the page-locked host-scalar block: sflag [cap], hflag [cap], hs [24][cap]
-   words (dsm16: 19 rows; dsm16s: 24), pts [8][40][cap] words (dsm16: rows
-   of 20 limbs, A and R; dsm16s: rows of 40, the doubled points' extended
-   coordinates too), pflag [2][cap], the go word (params.go) */
-#define HS_O_HS( cap )  ( 2UL*(cap) )
-#define HS_O_PTS( cap ) ( ( 2UL + 24UL*4UL )*(cap) )
-#define HS_O_PFL( cap ) ( ( 2UL + 24UL*4UL + 8UL*40UL*4UL )*(cap) )
-#define HS_O_GO( cap )  ( ( ( 2UL + 24UL*4UL + 8UL*40UL*4UL + 2UL )*(cap) + 15UL ) & ~15UL )
-#define HS_BYTES( cap ) ( HS_O_GO( cap ) + 16UL )
 
 struct fd_ed25519_hip_pipe {
   int           device;
@@ -327,9 +319,9 @@ pipe_slot_init( pipe_slot_t * s, int device, unsigned long sig_cap, unsigned lon
   TCHK( hipHostGetDevicePointer( (void **)&s->h_outb_dev, s->h_outb, 0U ), "hipHostGetDevicePointer" );
   /* the device-decode layout at the work arrays' stride (no points), or the
      host-decode one at the small stride: room for the larger */
-  TCHK( hipHostMalloc( (void **)&s->h_hs, HS_O_PTS( sig_cap )>HS_BYTES( FD_ED25519_HS_STRIDE ) ? HS_O_PTS( sig_cap )
-                                                                                               : HS_BYTES( FD_ED25519_HS_STRIDE ),
-                       hipHostMallocCoherent ), "hipHostMalloc" );
+  unsigned long hs_dev = fd_ed25519_hip_private_hs_bytes( sig_cap, 0 );
+  unsigned long hs_host = fd_ed25519_hip_private_hs_bytes( FD_ED25519_HS_STRIDE, 1 );
+  TCHK( hipHostMalloc( (void **)&s->h_hs, hs_dev>hs_host ? hs_dev : hs_host, hipHostMallocCoherent ), "hipHostMalloc" );
   TCHK( hipHostGetDevicePointer( (void **)&s->h_hs_dev, s->h_hs, 0U ), "hipHostGetDevicePointer" );
   TCHK( hipMalloc(     (void **)&s->d_outb, out_sz                       ), "hipMalloc" );
   p->sigs        = s->h_in + o_sigs;                   s->d_sigs   = s->d_in + o_sigs;
@@ -528,7 +520,8 @@ slot_check( fd_ed25519_hip_slot_t const * slot, unsigned long sig_cnt, unsigned 
   return FD_ED25519_HIP_OK;
 }
 
-/* A host-scalar batch (PIPE_HS_MAX above): the decompressions launched
+/* A host-scalar batch (PIPE_HS_MAX above; the sequence is
+   host/fd_ed25519_hip_hs.c's): the decompressions launched
    first, the scalars computed meanwhile, then dsm16 writing the signature
    codes into the page-locked output block -- or (PIPE_HD_MAX) dsm16
    launched first, waiting on the go word, and the scalars and
@@ -546,81 +539,23 @@ pipe_submit_hs( fd_ed25519_hip_pipe_t * pipe, pipe_slot_t * s, hipStream_t st ) 
               ? pipe_split : 0;
   /* the host block's stride: the work arrays' when the device decodes, a
      small one when every array is this thread's (FD_ED25519_HS_STRIDE) */
-  unsigned long sc = hd ? FD_ED25519_HS_STRIDE : cap;
-  volatile uint32_t * go = (volatile uint32_t *)( s->h_hs + HS_O_GO( sc ) );
-  if( !hd ) {
-    PF_SUB( pf_sub_launch, err = fd_ed25519_hip_private_hs_decode( s->eng, n, s->h_in_dev + o_sigs, s->h_in_dev + o_pubs,
-                                                                   (signed char *)s->h_outb_dev, st ) );
-    if( err ) return err;
-  } else {
-    /* dsm16 first, waiting on the go word while this thread computes
-       (params.go); every path below stores RUN or CANCEL */
-    *go = 0U;
-    if( split ) {
-      PF_SUB( pf_sub_launch, err = fd_ed25519_hip_private_hs_dsms( s->eng, split, n, s->h_in_dev + o_sigs, s->h_in_dev + o_pubs,
-                                                                   (signed char *)s->h_outb_dev, s->h_hs_dev,
-                                                                   s->h_hs_dev + sc,
-                                                                   (unsigned int const *)( s->h_hs_dev + HS_O_HS( sc ) ),
-                                                                   (int const *)( s->h_hs_dev + HS_O_PTS( sc ) ),
-                                                                   s->h_hs_dev + HS_O_PFL( sc ),
-                                                                   (unsigned int const *)( s->h_hs_dev + HS_O_GO( sc ) ), st ) );
-    } else {
-      PF_SUB( pf_sub_launch, err = fd_ed25519_hip_private_hs_dsm( s->eng, n, s->h_in_dev + o_sigs, s->h_in_dev + o_pubs,
-                                                                  (signed char *)s->h_outb_dev, s->h_hs_dev,
-                                                                  s->h_hs_dev + sc,
-                                                                  (unsigned int const *)( s->h_hs_dev + HS_O_HS( sc ) ),
-                                                                  (int const *)( s->h_hs_dev + HS_O_PTS( sc ) ),
-                                                                  s->h_hs_dev + HS_O_PFL( sc ),
-                                                                  (unsigned int const *)( s->h_hs_dev + HS_O_GO( sc ) ), st ) );
-    }
-    if( err ) return err;
+  fd_ed25519_hip_hs_t hb;
+  fd_ed25519_hip_private_hs_init( &hb, s->h_hs, hd ? FD_ED25519_HS_STRIDE : cap, hd, n, split,
+                                  !fd_ed25519_hip_private_codes_portable( s->eng ) );
+  PF_SUB( pf_sub_launch, err = fd_ed25519_hip_private_hs_begin( &hb, s->eng, s->h_hs_dev, s->h_in_dev + o_sigs,
+                                                                s->h_in_dev + o_pubs, (signed char *)s->h_outb_dev, st ) );
+  if( err ) return err;
+  int all = 1, dbits = fd_ed25519_hip_private_half_dbits( s->eng );
+  unsigned char const * enc[ 2UL*FD_ED25519_HS_DECODE_MAX ];   /* A and R of each signature, side by side */
+  for( unsigned long i=0UL; i<n && all; i++ ) {
+    all = fd_ed25519_hip_private_hs_scalars( &hb, i, slot->sigs + 64UL*i, slot->pubs + 32UL*i,
+                                             slot->msgs + slot->msg_off[ i ], slot->msg_sz[ i ], dbits );
+    if( hd ) { enc[ 2UL*i ] = slot->pubs + 32UL*i; enc[ 2UL*i+1UL ] = slot->sigs + 64UL*i; }
   }
-  unsigned char * hsf = s->h_hs, * hhf = s->h_hs + sc;
-  uint32_t *      hs  = (uint32_t *)( s->h_hs + HS_O_HS( sc ) );
-  int dbits = fd_ed25519_hip_private_half_dbits( s->eng );
-  for( unsigned long i=0UL; i<n; i++ ) {
-    uint32_t rec[ 32 ];
-    if( !fd_ed25519_hip_private_hsrec( slot->sigs + 64UL*i, slot->pubs + 32UL*i, slot->msgs + slot->msg_off[ i ],
-                                       slot->msg_sz[ i ], dbits, rec ) ) {
-      if( hd ) __atomic_store_n( go, FD_ED25519_GO_CANCEL, __ATOMIC_RELEASE );
-      return 0;
-    }
-    if( split ) fd_ed25519_hip_private_hssplit( rec, split, hs, sc, i );
-    else for( int w=0; w<19; w++ ) hs[ (unsigned long)w*sc + i ] = rec[ 8 + w ];
-    hsf[ i ] = (unsigned char)rec[ 27 ];
-    hhf[ i ] = (unsigned char)rec[ 28 ];
-  }
-  if( hd ) {   /* A and R of each signature, side by side */
-    unsigned char const * enc[ 2UL*PIPE_HD_CAP ];
-    int32_t       pt[ 2UL*PIPE_HD_CAP ][ 20 ], ptx[ 2UL*PIPE_HD_CAP*3UL ][ 40 ];
-    unsigned char fl[ 2UL*PIPE_HD_CAP ];
-    int nx = split ? split/2 - 1 : 0, step = split==4 ? 66 : 33;
-    for( unsigned long i=0UL; i<n; i++ ) { enc[ 2UL*i ] = slot->pubs + 32UL*i; enc[ 2UL*i+1UL ] = slot->sigs + 64UL*i; }
-    fd_ed25519_hip_private_hsdec3_n( enc, 2UL*n, !fd_ed25519_hip_private_codes_portable( s->eng ), &pt[0][0],
-                                     split ? &ptx[0][0] : NULL, nx, step, fl );
-    int32_t * pts = (int32_t *)( s->h_hs + HS_O_PTS( sc ) );
-    unsigned char * pfl = s->h_hs + HS_O_PFL( sc );
-    unsigned long rs = split ? 40UL : 20UL;   /* the row stride in limbs: dsm16s's, dsm16's */
-    for( unsigned long i=0UL; i<n; i++ )
-      for( unsigned long side=0UL; side<2UL; side++ ) {   /* rows 2i + side: A, R, A_1, R_1, .. */
-        unsigned long pi = 2UL*i + side;
-        for( unsigned long l=0UL; l<20UL; l++ ) pts[ ( side*rs + l )*sc + i ] = pt[ pi ][ l ];
-        for( int m=1; m<=nx; m++ )
-          for( unsigned long l=0UL; l<40UL; l++ )
-            pts[ ( ( 2UL*(unsigned long)m + side )*40UL + l )*sc + i ] = ptx[ pi*(unsigned long)nx + (unsigned long)(m-1) ][ l ];
-        pfl[ side*sc + i ] = fl[ pi ];
-      }
-  }
-  if( hd ) {
-    __atomic_store_n( go, FD_ED25519_GO_RUN, __ATOMIC_RELEASE );
-  } else {
-    PF_SUB( pf_sub_launch, err = fd_ed25519_hip_private_hs_dsm( s->eng, n, s->h_in_dev + o_sigs, s->h_in_dev + o_pubs,
-                                                                (signed char *)s->h_outb_dev, s->h_hs_dev,
-                                                                s->h_hs_dev + sc,
-                                                                (unsigned int const *)( s->h_hs_dev + HS_O_HS( sc ) ),
-                                                                NULL, NULL, NULL, st ) );
-    if( err ) return err;
-  }
+  if( all && hd ) fd_ed25519_hip_private_hs_points( &hb, enc );
+  PF_SUB( pf_sub_launch, err = fd_ed25519_hip_private_hs_end( &hb, all ) );
+  if( err ) return err;
+  if( !all ) return 0;
   s->host_combine = slot->txn_cnt ? 1 : 0;
   TCHK( hipEventRecord( s->ev, st ), "hipEventRecord" );
 #ifdef FD_ED25519_HIP_AB_STAGE_TRACE
@@ -631,24 +566,12 @@ pipe_submit_hs( fd_ed25519_hip_pipe_t * pipe, pipe_slot_t * s, hipStream_t st ) 
   return 1;
 }
 
-/* batch_single_msg's rule per transaction (fd_ed25519_user.c:231-309, the
-   device's fd_ed25519_txn_combine_kernel): 0 or > 16 signatures ERR_SIG;
-   else the first error other than ERR_MSG in signature order, else ERR_MSG
-   if any signature had it, else SUCCESS */
+/* batch_single_msg's rule per transaction of a host-scalar batch */
 static void
 host_combine( fd_ed25519_hip_slot_t * slot ) {
-  for( unsigned long t=0UL; t<slot->txn_cnt; t++ ) {
-    unsigned int f = slot->txn_first[ t ], n = slot->txn_sig_cnt[ t ];
-    int code = FD_ED25519_SUCCESS, msg_fail = 0;
-    if( n==0U || n>16U ) code = FD_ED25519_ERR_SIG;
-    else for( unsigned int j=0U; j<n; j++ ) {
-      int c = slot->sig_out[ f + j ];
-      if( c==FD_ED25519_ERR_MSG ) msg_fail = 1;
-      else if( c!=FD_ED25519_SUCCESS ) { code = c; break; }
-    }
-    if( code==FD_ED25519_SUCCESS && msg_fail ) code = FD_ED25519_ERR_MSG;
-    slot->txn_out[ t ] = (signed char)code;
-  }
+  for( unsigned long t=0UL; t<slot->txn_cnt; t++ )
+    slot->txn_out[ t ] = (signed char)fd_ed25519_hip_private_hs_combine( slot->sig_out, slot->txn_first[ t ],
+                                                                         slot->txn_sig_cnt[ t ] );
 }
 
 int

@@ -207,8 +207,9 @@ typedef struct fd_ed25519_hip_engine fd_ed25519_hip_engine_t;
    payload; 5: shlink protocol word and creator, vservice lifecycle and
    end codes; 6: vservice links_per_thread; 7: vservice link_cpus; 8:
    vservice stats' leaked_on_hang, the drop-ins' device-lost state, the
-   dsm16 form and its flag; 9: shlink protocol 6, flock-owned links).  A
-   consumer checks
+   dsm16 form and its flag; 9: shlink protocol 6, flock-owned links; 10:
+   the drop-in's and the pipe's host-scalar, host-decode and split-waves
+   setters, latency_set_cpus).  A consumer checks
    the library it loaded against the header it was built with:
    fd_ed25519_hip_abi_check( FD_ED25519_HIP_ABI_VERSION,
    sizeof(fd_ed25519_hip_slot_t), sizeof(fd_ed25519_hip_info_t),

@@ -6,7 +6,8 @@ fewest-signature launches (fd_ed25519_hip_dropin_set_host_decode,
 host/fd_ed25519_hip_hsdec.cc) decompress A and R on the calling thread too
 and launch the group equation alone, reading the points in place -- over
 eight or four waves on A and R doubled by the host every 33 or 66 bits
-(dsm16s, fd_ed25519_hip_dropin_set_split_waves) or in dsm16's two.  Every
+(dsm16s, fd_ed25519_hip_dropin_set_split_waves) or in dsm16's two (the
+sequence and the block's layout: host/fd_ed25519_hip_hs.c).  Every
 fixture class -- the reference's vectors, the adversarial set,
 mixed-order points, k needing long |d| -- through fd_ed25519_verify with
 each mode on (the default) and off, code by code against the reference's

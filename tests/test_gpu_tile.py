@@ -354,8 +354,9 @@ def test_pipe_stages_in_place_and_rejects_out_of_range(tile, adversarial):
                               "host-scalars", "device-path"])
 def test_pipe_tiny_batches_every_path(tile, adversarial, mixed_order, batch, hs, hd, waves):
     """Batches of one to four signatures (a tile at a low load), through the
-    host-scalar path (prep16's decode blocks + dsm16 reading the staged
-    block in place, transaction codes combined on the host), with the
+    host-scalar path (host/fd_ed25519_hip_hs.c: prep16's decode blocks +
+    dsm16 reading the staged block in place, transaction codes combined on
+    the host), with the
     decompressions on the submitting thread too for batches of at most hd
     signatures (the group equation alone, reading the points in place: over
     dsm16s's four or eight waves or dsm16's two), and through the device path: single signatures of the adversarial and mixed-order sets,
@@ -424,6 +425,52 @@ def test_pipe_tiny_batches_every_path(tile, adversarial, mixed_order, batch, hs,
         p.close()
         bad = [(k, results.get(k), j[4]) for k, j in enumerate(jobs) if [int(x) for x in results.get(k, [])] != j[4]]
         assert not bad, bad[:10]
+    finally:
+        tile.pipe_set_host_scalars(4)
+        tile.pipe_set_host_decode(4)
+        tile.pipe_set_split_waves(2)
+
+
+@pytest.mark.parametrize("waves", [2, 4])
+def test_pipe_one_slot_alternates_host_scalar_strides(tile, adversarial, mixed_order, waves):
+    """One slot takes batches of 1, 3, 5, 2, 4, 1, .. signatures in turn, so
+    its one host-scalar block (host/fd_ed25519_hip_hs.c) is written
+    host-decoded at the small stride (1, 2), then device-decoded at sig_cap's
+    (3, 4), then left alone by the device path (5), over and over: nothing
+    one layout leaves behind may reach the next.  Every signature's code
+    against the reference's."""
+    tile.pipe_set_host_scalars(4)
+    tile.pipe_set_host_decode(2)
+    tile.pipe_set_split_waves(waves)
+    try:
+        zmax = max(int(d["msg_sz"].max()) for d in (adversarial, mixed_order))
+        p = tile.Pipe(0, slot_cnt=1, sig_cap=16, msg_cap=5 * zmax, txn_cap=16)
+        sizes, bad, batches = [1, 3, 5, 2, 4], [], 0
+        for name, d in (("adversarial", adversarial), ("mixed_order", mixed_order)):
+            i = 0
+            for b in range(30):
+                k = sizes[b % 5]
+                s = p.acquire()
+                assert s is not None
+                a, pos = tile.Pipe.arrays(s), 0
+                for q in range(k):
+                    o, z = int(d["msg_off"][i + q]), int(d["msg_sz"][i + q])
+                    a["msgs"][pos:pos + z] = d["msgs"][o:o + z]
+                    a["msg_off"][q], a["msg_sz"][q] = pos, z
+                    a["sigs"][64 * q:64 * q + 64] = d["sigs"][i + q]
+                    a["pubs"][32 * q:32 * q + 32] = d["pubs"][i + q]
+                    pos += z
+                assert p.submit(s, k, pos) == 0
+                done = p.poll(True)
+                got = [int(x) for x in tile.Pipe.arrays(done)["sig_out"][:k]]
+                p.release(done)
+                want = [int(x) for x in d["codes_avx512"][i:i + k]]
+                if got != want:
+                    bad.append((name, i, k, got, want))
+                i += k
+                batches += 1
+        p.close()
+        assert batches == 60 and not bad, bad[:10]
     finally:
         tile.pipe_set_host_scalars(4)
         tile.pipe_set_host_decode(4)
