@@ -138,6 +138,67 @@ FD_DEV int pop_digit(uint32_t (&d)[8]) {
   return v;
 }
 
+/* The 160-bit forms the half-size dsm loops use (c, |d|, s_lo, s_hi). */
+
+/* x << SH for a 160-bit value known to stay below 2^160 */
+template <int SH>
+FD_DEV void shl160(uint32_t (&out)[5], const uint32_t (&x)[5]) {
+  constexpr int W = SH / 32, B = SH % 32;
+#pragma unroll
+  for (int i = 4; i >= 0; i--) {
+    const uint32_t hi = i - W >= 0 ? x[i - W] : 0u;
+    const uint32_t lo = i - W - 1 >= 0 ? x[i - W - 1] : 0u;
+    out[i] = B ? __builtin_amdgcn_alignbit(hi, lo, 32 - B) : hi;
+  }
+}
+
+/* x << s for 0 < s < 32 (wave-uniform s), the value staying below 2^160 */
+FD_DEV void shl160v(uint32_t (&out)[5], const uint32_t (&x)[5], int s) {
+#pragma unroll
+  for (int i = 4; i > 0; i--) out[i] = __builtin_amdgcn_alignbit(x[i], x[i - 1], 32 - s);
+  out[0] = x[0] << s;
+}
+
+/* signed recoding of a 160-bit value in radix 2^BITS, digits packed as
+   BITS-bit two's complement (the carry out of the top digit is dropped:
+   the caller reads the top digit unsigned where it may reach 2^(BITS-1)) */
+template <int BITS>
+FD_DEV void recode160(uint32_t (&out)[5], const uint32_t (&x)[5]) {
+  constexpr uint32_t M = (1u << BITS) - 1u;
+  constexpr int PER = 32 / BITS;
+  int carry = 0;
+#pragma unroll
+  for (int w = 0; w < 5; w++) {
+    uint32_t packed = 0;
+#pragma unroll
+    for (int q = 0; q < PER; q++) {
+      int e = (int)((x[w] >> (BITS * q)) & M) + carry;
+      carry = (e + (1 << (BITS - 1))) >> BITS;
+      e -= carry << BITS;
+      packed |= ((uint32_t)e & M) << (BITS * q);
+    }
+    out[w] = packed;
+  }
+}
+
+template <int BITS>
+FD_DEV uint32_t pop160u(uint32_t (&d)[5]) {
+  const uint32_t v = d[4] >> (32 - BITS);
+#pragma unroll
+  for (int w = 4; w > 0; w--) d[w] = __builtin_amdgcn_alignbit(d[w], d[w - 1], 32 - BITS);
+  d[0] <<= BITS;
+  return v;
+}
+
+template <int BITS>
+FD_DEV int pop160(uint32_t (&d)[5]) {
+  const int v = ((int32_t)d[4]) >> (32 - BITS);
+#pragma unroll
+  for (int w = 4; w > 0; w--) d[w] = __builtin_amdgcn_alignbit(d[w], d[w - 1], 32 - BITS);
+  d[0] <<= BITS;
+  return v;
+}
+
 /* ------------------------------------------------------------------------
    Tables */
 

@@ -80,7 +80,11 @@ FD_DEV void sc_reduce512(uint32_t (&out)[8], const uint32_t (&in)[16]) {
 #pragma unroll
   for (int i = 0; i <= 10; i++) sc_carry_f(s, i);
 
-  /* pack 12 digits of 21 bits (s[i] in [0,2^21)) */
+  /* pack 12 digits of 21 bits: s[0..10] in [0,2^21); s[11], which the last
+     pass does not carry out of, holds bits 231.. of the residue, in
+     [0,2^21] -- exactly 2^21 for every residue in [2^252, L).  Digit 11
+     lands at bit 7 of word 7 with nothing packed above it, so v << sh keeps
+     its bit 21 (bit 252 of the result). */
   uint32_t w[8] = {0, 0, 0, 0, 0, 0, 0, 0};
 #pragma unroll
   for (int i = 0; i < 12; i++) {

@@ -142,6 +142,13 @@ pair_ok( uint32_t const k[ 8 ], uint32_t const ( &c )[ FD_HALF_TW ], uint32_t co
 
 } /* namespace */
 
+/* mod_l for the tests (tests/test_modl.py chooses inputs that take the
+   add-back branch, which no hash does); in no public header */
+extern "C" void
+fd_ed25519_hip_private_mod_l( uint32_t out[ 8 ], uint32_t const * x, int n ) {
+  mod_l( out, x, n );
+}
+
 /* 1: rec holds the signature's record; 0: its k has no half-size pair
    within dbits (about 1e-6 of signatures at 151 bits): the caller takes the
    device's own path for that launch (whose full-length form handles it). */
