@@ -323,6 +323,48 @@ int fd_ed25519_hip_launch_txn_combine( int8_t const * d_sig_codes, uint32_t cons
    fd_ed25519_hip_diag_half_scalars) */
 int fd_ed25519_hip_launch_diag_half( uint32_t const * d_k, uint32_t * d_out, uint64_t n, int dbits, void * stream );
 
+/* diagnostic (tests/test_gpu_dsm_diag.py): the product's own dsm kernels on
+   work arrays the caller wrote, every array [row][n] (stride cap = n) in
+   host memory, copied to device temporaries and launched as the dsm phase
+   alone -- no hash, no scalar search, no decode.  form: */
+#define FD_ED25519_DIAG_DSM_WIDE   0   /* dsm_kernel (small 0): fix_list / fix_cnt from hflag, work_ctr 0  */
+#define FD_ED25519_DIAG_DSM_QUAD   1   /* dsm4, then dsm_kernel's scan for the full-length items          */
+#define FD_ED25519_DIAG_DSM_OCT    2   /* dsm8, then the scan                                             */
+#define FD_ED25519_DIAG_DSM_R16    3   /* dsm16 (full_in_prep 0, hs_host 0), then the scan                */
+#define FD_ED25519_DIAG_DSM_SPLIT4 4   /* dsm16s<4> */
+#define FD_ED25519_DIAG_DSM_SPLIT8 8   /* dsm16s<8> */
+/*   sflag [n], hflag [n], pflag [2][n] as in fd_ed25519_verify_params_t;
+     forms 0..3: pts [2][20][n], hs [19][n], and for the full-length items
+       (hflag bit 1) k [8][n] and S [n][64] (R||S, only S read); k and S
+       may be NULL when hflag marks none;
+     split forms: pts [S][40][n] and hs [24][n] as hsdec3_n / hssplit write
+       them, no full-length item, k and S unused.
+   params.go stays NULL.  out [n]: the codes (a signature no kernel wrote a
+   code for keeps FD_ED25519_DIAG_DSM_UNWRITTEN).
+   diag_dsm_check is the whole validation, host only (no engine, no GPU);
+   diag_dsm launches nothing it refuses (FD_ED25519_HIP_ERR_INVAL): flags
+   outside their bits; n == 0 or above n_max (diag_dsm passes what the
+   engine's form limits and lane tables admit); forms 0..3, half-size
+   items: c >= 2^FD_HALF_BITS, |d| >= 2^half_dbits, s_lo >= 2^144, s_lo +
+   2^144 s_hi >= 2^253; full-length items: k >= 2^253, S >= L with sflag
+   set (recode_radix65536's S < L); split forms: a split scalar so long
+   that 160 - 4 W - SH0 < 8 (S = 4: 88 bits or more, S = 8: 56 or more), a
+   chunk of s' >= 2^CB, a full-length flag; affine point limbs outside
+   what a decode leaves (x: |limb| <= 1.01 units of 2^25 / 2^24, tight; y:
+   above that or at 2^26 / 2^25, fe_frombytes's), extended point limbs
+   (split forms, rows >= 2) not tight (table16_build_p3's). */
+#define FD_ED25519_DIAG_DSM_UNWRITTEN 0x55
+int fd_ed25519_hip_private_diag_dsm_check( int form, unsigned long n, unsigned long n_max, int half_dbits,
+                                           unsigned char const * sflag, unsigned char const * hflag,
+                                           unsigned char const * pflag, int32_t const * pts, uint32_t const * hs,
+                                           uint32_t const * k, unsigned char const * S );
+/* what n_max diag_dsm passes for this engine and form (0: the form is not available) */
+unsigned long fd_ed25519_hip_private_diag_dsm_nmax( struct fd_ed25519_hip_engine * e, int form );
+int fd_ed25519_hip_private_diag_dsm( struct fd_ed25519_hip_engine * e, int form, unsigned long n,
+                                     unsigned char const * sflag, unsigned char const * hflag,
+                                     unsigned char const * pflag, int32_t const * pts, uint32_t const * hs,
+                                     uint32_t const * k, unsigned char const * S, signed char * out );
+
 /* ---- raw transactions (fd_ed25519_txn.hip) ---- */
 
 /* per-transaction code for a payload fd_txn_parse rejects (never an

@@ -834,6 +834,165 @@ fd_ed25519_hip_private_want_dsms( fd_ed25519_hip_engine_t * e, int waves ) {
   return e->btabs[set][0] ? 1 : 0;
 }
 
+/* ---- diagnostic: the dsm kernels on the caller's work arrays
+        (fd_ed25519_hip_internal.h; tests/test_gpu_dsm_diag.py) ---- */
+
+/* bits of the value in rows [row, row+words) of column j */
+static int
+diag_bitlen( uint32_t const * a, unsigned long row, int words, unsigned long cap, unsigned long j ) {
+  for( int w=words-1; w>=0; w-- ) {
+    uint32_t x = a[ ( row + (unsigned long)w )*cap + j ];
+    if( x ) return 32*w + 32 - __builtin_clz( x );
+  }
+  return 0;
+}
+
+/* a coordinate's ten limbs at rows [row, row+10): tight (|limb| <= 1.01
+   units, fd25519_fe.h), or with frombytes not 0 also fe_frombytes's
+   unsigned limbs (< 2^26 / 2^25) */
+static int
+diag_limbs_ok( int32_t const * pts, unsigned long row, unsigned long cap, unsigned long j, int frombytes ) {
+  for( int l=0; l<10; l++ ) {
+    int64_t unit = ( l & 1 ) ? ( 1L<<24 ) : ( 1L<<25 );
+    int64_t tight = unit + unit/100L, v = pts[ ( row + (unsigned long)l )*cap + j ];
+    if( v < -tight ) return 0;
+    if( v > ( frombytes ? 2L*unit - 1L : tight ) ) return 0;
+  }
+  return 1;
+}
+
+static int
+diag_lt_l( unsigned char const s[ 32 ] ) {
+  static unsigned char const l[ 32 ] = { 0xed, 0xd3, 0xf5, 0x5c, 0x1a, 0x63, 0x12, 0x58, 0xd6, 0x9c, 0xf7, 0xa2, 0xde, 0xf9,
+                                         0xde, 0x14, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0x10 };
+  for( int i=31; i>=0; i-- ) if( s[ i ]!=l[ i ] ) return s[ i ]<l[ i ];
+  return 0;
+}
+
+int
+fd_ed25519_hip_private_diag_dsm_check( int form, unsigned long n, unsigned long n_max, int half_dbits,
+                                       unsigned char const * sflag, unsigned char const * hflag,
+                                       unsigned char const * pflag, int32_t const * pts, uint32_t const * hs,
+                                       uint32_t const * k, unsigned char const * S ) {
+  int split = form==FD_ED25519_DIAG_DSM_SPLIT4 ? 4 : form==FD_ED25519_DIAG_DSM_SPLIT8 ? 8 : 0;
+  if( !split && ( form<FD_ED25519_DIAG_DSM_WIDE || form>FD_ED25519_DIAG_DSM_R16 ) ) return FD_ED25519_HIP_ERR_INVAL;
+  /* FD_HALF_BITS <= half_dbits <= FD_HALF_DBITS_MAX (fd25519_half.h) */
+  if( !n || n>n_max || half_dbits<131 || half_dbits>151 ) return FD_ED25519_HIP_ERR_INVAL;
+  if( !sflag || !hflag || !pflag || !pts || !hs ) return FD_ED25519_HIP_ERR_INVAL;
+  for( unsigned long j=0UL; j<n; j++ ) {
+    if( sflag[ j ]>1 || hflag[ j ]>3 || pflag[ j ]>3 || pflag[ n + j ]>3 ) return FD_ED25519_HIP_ERR_INVAL;
+    if( !split ) {
+      for( unsigned long which=0UL; which<2UL; which++ )
+        if( !diag_limbs_ok( pts, which*20UL, n, j, 0 ) || !diag_limbs_ok( pts, which*20UL + 10UL, n, j, 1 ) )
+          return FD_ED25519_HIP_ERR_INVAL;
+      if( hflag[ j ] & 2 ) {   /* full-length form: k in radix 16, S in radix 2^16 */
+        if( !k || !S || diag_bitlen( k, 0UL, 8, n, j )>253 ) return FD_ED25519_HIP_ERR_INVAL;
+        if( sflag[ j ] && !diag_lt_l( S + 64UL*j + 32UL ) ) return FD_ED25519_HIP_ERR_INVAL;
+      } else if( diag_bitlen( hs, 0UL, 5, n, j )>131 /* FD_HALF_BITS */ || diag_bitlen( hs, 5UL, 5, n, j )>half_dbits ||
+                 diag_bitlen( hs, 10UL, 5, n, j )>FD_ED25519_BTABW_SHIFT ||
+                 diag_bitlen( hs, 15UL, 4, n, j )>253-FD_ED25519_BTABW_SHIFT ) {
+        return FD_ED25519_HIP_ERR_INVAL;
+      }
+    } else {
+      /* dsm16s<S>'s constants */
+      int kw = split==4 ? 3 : 2, sh0 = split==4 ? 64 : 96;
+      if( hflag[ j ] & 2 ) return FD_ED25519_HIP_ERR_INVAL;
+      for( int q=0; q<split; q++ ) {
+        int w = ( diag_bitlen( hs, (unsigned long)( kw*q ), kw, n, j ) + 4 ) >> 2;
+        if( 160 - 4*w - sh0 < 8 ) return FD_ED25519_HIP_ERR_INVAL;
+        if( split==4 && hs[ ( 12UL + 3UL*(unsigned long)q + 2UL )*n + j ]>0xffU ) return FD_ED25519_HIP_ERR_INVAL;   /* CB 72 */
+        unsigned long row = (unsigned long)q*40UL;   /* pts row 2 part + side */
+        if( q<2 ) {
+          if( !diag_limbs_ok( pts, row, n, j, 0 ) || !diag_limbs_ok( pts, row + 10UL, n, j, 1 ) ) return FD_ED25519_HIP_ERR_INVAL;
+        } else {
+          for( unsigned long c=0UL; c<4UL; c++ ) if( !diag_limbs_ok( pts, row + 10UL*c, n, j, 0 ) ) return FD_ED25519_HIP_ERR_INVAL;
+        }
+      }
+    }
+  }
+  return FD_ED25519_HIP_OK;
+}
+
+unsigned long
+fd_ed25519_hip_private_diag_dsm_nmax( fd_ed25519_hip_engine_t * e, int form ) {
+  if( !e ) return 0UL;
+  uint64_t m = e->max_chunk;
+  uint64_t room = lane_atab_bytes( e ) / (4UL * FD_ED25519_QUAD_LANE_BYTES);   /* dsm4's and dsm8's lane tables */
+  switch( form ) {
+  case FD_ED25519_DIAG_DSM_WIDE: break;   /* the grid, and so the lane tables it needs, never above the engine's */
+  case FD_ED25519_DIAG_DSM_QUAD: if( e->quad_max<m ) m = e->quad_max; if( room<m ) m = room; break;
+  case FD_ED25519_DIAG_DSM_OCT:  if( e->quad_max<m ) m = e->quad_max; if( e->oct_max<m ) m = e->oct_max; if( room<m ) m = room; break;
+  case FD_ED25519_DIAG_DSM_R16:  if( e->quad_max<m ) m = e->quad_max; if( e->r16_max<m ) m = e->r16_max; break;
+  case FD_ED25519_DIAG_DSM_SPLIT4:
+  case FD_ED25519_DIAG_DSM_SPLIT8:
+    if( e->r16_max<m ) m = e->r16_max;
+    if( !fd_ed25519_hip_private_want_dsms( e, form ) ) m = 0UL;
+    break;
+  default: m = 0UL;
+  }
+  return m;
+}
+
+int
+fd_ed25519_hip_private_diag_dsm( fd_ed25519_hip_engine_t * e, int form, unsigned long n,
+                                 unsigned char const * sflag, unsigned char const * hflag,
+                                 unsigned char const * pflag, int32_t const * pts, uint32_t const * hs,
+                                 uint32_t const * k, unsigned char const * S, signed char * out ) {
+  if( !e || !out ) return FD_ED25519_HIP_ERR_INVAL;
+  int err = fd_ed25519_hip_private_diag_dsm_check( form, n, fd_ed25519_hip_private_diag_dsm_nmax( e, form ),
+                                                   engine_half_dbits( e ), sflag, hflag, pflag, pts, hs, k, S );
+  if( err ) {
+    snprintf( fd_ed25519_hip_errbuf, sizeof(fd_ed25519_hip_errbuf), "diag_dsm: arrays outside the dsm kernels' contracts" );
+    return err;
+  }
+  int split = form==FD_ED25519_DIAG_DSM_SPLIT4 || form==FD_ED25519_DIAG_DSM_SPLIT8 ? form : 0;
+  HIPCHK( hipSetDevice( e->device ), "hipSetDevice" );
+  /* the full-length items, as the scalar phase would list them */
+  uint32_t * fix = (uint32_t *)calloc( n + 2UL, 4UL );
+  if( !fix ) return FD_ED25519_HIP_ERR_NOMEM;
+  uint32_t nfix = 0U;
+  for( unsigned long j=0UL; j<n; j++ ) if( hflag[ j ] & 2 ) fix[ 2UL + nfix++ ] = (uint32_t)j;
+  fix[ 0 ] = nfix; fix[ 1 ] = 0U;   /* fix_cnt, work_ctr: adjacent words, then the list */
+  /* one allocation, every array 256-byte aligned in it */
+  size_t sz[ 9 ] = { n, n, 2UL*n, ( split ? (size_t)split*40UL : 40UL )*4UL*n, ( split ? 24UL : 19UL )*4UL*n, 8UL*4UL*n,
+                     64UL*n, 4UL*n + 8UL, n };
+  size_t off[ 9 ], total = 0UL;
+  for( int i=0; i<9; i++ ) { off[ i ] = total; total += ( sz[ i ] + 255UL ) & ~(size_t)255UL; }
+  uint8_t * d = NULL;
+  hipError_t he = hipMalloc( (void **)&d, total );
+  if( he==hipSuccess ) he = hipMemsetAsync( d, 0, total, e->stream );
+  if( he==hipSuccess ) he = hipMemsetAsync( d + off[ 8 ], FD_ED25519_DIAG_DSM_UNWRITTEN, n, e->stream );
+  void const * src[ 8 ] = { sflag, hflag, pflag, pts, hs, k, S, fix };
+  for( int i=0; i<8 && he==hipSuccess; i++ )
+    if( src[ i ] ) he = hipMemcpyAsync( d + off[ i ], src[ i ], sz[ i ], hipMemcpyHostToDevice, e->stream );
+  if( he==hipSuccess ) {
+    fd_ed25519_verify_params_t p;
+    memset( &p, 0, sizeof(p) );
+    params_tables( e, &p );
+    p.cap = n; p.n = n; p.base = 0UL;
+    p.sflag = d + off[ 0 ]; p.hflag = d + off[ 1 ]; p.pflag = d + off[ 2 ]; p.pts = (int32_t *)( d + off[ 3 ] );
+    p.hs = (uint32_t *)( d + off[ 4 ] ); p.k = (uint32_t *)( d + off[ 5 ] ); p.sigs = d + off[ 6 ];
+    p.fix_cnt = (uint32_t *)( d + off[ 7 ] ); p.work_ctr = p.fix_cnt + 1; p.fix_list = p.fix_cnt + 2;
+    p.out = (int8_t *)( d + off[ 8 ] );
+    p.atab = e->lane[0].d_atab;
+    if( split ) {
+      p.small = 3; p.hs_host = 1;
+      for( int q=0; q<8; q++ ) p.btabq[q] = e->btabs[ split_set( split ) ][q];
+      he = (hipError_t)fd_ed25519_hip_launch_dsm16s( &p, split, e->stream );
+    } else {
+      p.small = form;   /* full_in_prep 0, hs_host 0: the flag scan follows dsm16 */
+      he = (hipError_t)fd_ed25519_hip_launch_phase( &p, FD_ED25519_PHASE_DSM, e->dsm_grid, e->stream );
+    }
+  }
+  if( he==hipSuccess ) he = hipMemcpyAsync( out, d + off[ 8 ], n, hipMemcpyDeviceToHost, e->stream );
+  hipError_t se = hipStreamSynchronize( e->stream );
+  if( he==hipSuccess ) he = se;
+  hipFree( d );
+  free( fix );
+  if( he!=hipSuccess ) return hip_fail( he, "diag_dsm" );
+  return FD_ED25519_HIP_OK;
+}
+
 int
 fd_ed25519_hip_verify_digests_dev( fd_ed25519_hip_engine_t * e, unsigned long n, unsigned char const * digests,
                                    unsigned char const * sigs, unsigned char const * pubs, signed char * out,

@@ -85,6 +85,10 @@ _lib.fd_ed25519_hip_memcpy.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.
                                        ctypes.c_int]
 _lib.fd_ed25519_hip_device_clock_mhz.argtypes = [ctypes.c_void_p]
 _lib.fd_ed25519_hip_diag_half_scalars.argtypes = [ctypes.c_void_p, _u8p, ctypes.c_ulong, _u8p]
+_lib.fd_ed25519_hip_private_diag_dsm.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_ulong] + [_u8p] * 8
+_lib.fd_ed25519_hip_private_diag_dsm_nmax.argtypes = [ctypes.c_void_p, ctypes.c_int]
+_lib.fd_ed25519_hip_private_diag_dsm_nmax.restype = ctypes.c_ulong
+_lib.fd_ed25519_hip_private_diag_dsm_check.argtypes = [ctypes.c_int, ctypes.c_ulong, ctypes.c_ulong, ctypes.c_int] + [_u8p] * 7
 _lib.fd_ed25519_hip_strerror.argtypes = [ctypes.c_int]
 _lib.fd_ed25519_hip_strerror.restype = ctypes.c_char_p
 _lib.fd_ed25519_hip_last_error.restype = ctypes.c_char_p
@@ -272,6 +276,29 @@ class Engine:
             _check(_lib.fd_ed25519_hip_diag_half_scalars(self._h, k.ctypes.data_as(_u8p), len(k),
                                                          out.ctypes.data_as(_u8p)))
         return out
+
+    def diag_dsm(self, form, sflag, hflag, pflag, pts, hs, k=None, S=None):
+        """Diagnostic: the dsm phase alone on the caller's work arrays
+        (fd_ed25519_hip_private_diag_dsm, csrc/fd_ed25519_hip_internal.h):
+        form 0 wide, 1 quad, 2 oct, 3 r16, 4 / 8 the split forms; every
+        array [rows][n]; returns the int8 codes [n].  Arrays outside the
+        kernels' contracts raise HipError before anything is launched."""
+        sflag, hflag = _c(sflag, np.uint8).reshape(-1), _c(hflag, np.uint8).reshape(-1)
+        n = len(sflag)
+        rows_p, rows_h = (int(form) * 40, 24) if form in (4, 8) else (40, 19)
+        pflag, pts, hs = _c(pflag, np.uint8).reshape(-1), _c(pts, np.int32).reshape(-1), _c(hs, np.uint32).reshape(-1)
+        assert len(hflag) == n and len(pflag) == 2 * n and len(pts) == rows_p * n and len(hs) == rows_h * n
+        k = None if k is None else _c(k, np.uint32).reshape(-1)
+        S = None if S is None else _c(S, np.uint8).reshape(-1)
+        assert (k is None or len(k) == 8 * n) and (S is None or len(S) == 64 * n)
+        out = np.zeros(max(n, 1), dtype=np.int8)
+        _check(_lib.fd_ed25519_hip_private_diag_dsm(self._h, int(form), n, _ptr(sflag), _ptr(hflag), _ptr(pflag),
+                                                    _ptr(pts), _ptr(hs), _ptr(k), _ptr(S), _ptr(out)))
+        return out[:n]
+
+    def diag_dsm_nmax(self, form):
+        """the most signatures diag_dsm takes in that form on this engine"""
+        return _lib.fd_ed25519_hip_private_diag_dsm_nmax(self._h, int(form))
 
     def clock_mhz(self):
         return _lib.fd_ed25519_hip_device_clock_mhz(self._h)
