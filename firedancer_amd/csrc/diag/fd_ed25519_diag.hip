@@ -178,7 +178,7 @@ __global__ void __launch_bounds__(64) diag_sc_kernel(const uint32_t* in, uint32_
   if (OP == SC_OP_RECODE65536) { recode_radix65536(d, s); pop_all<16>(o, d); }
 }
 
-/* ---- digits160: dsm_half_one's prologue and pops, one lane per case -------
+/* ---- digits160: the 4-bit forms' (dsm4, dsm8, dsm16) prologue and pops, one lane per case
    in  11 words: c[5], |d|[5], W (33..38, checked on the host)
    out 80 words: c's W digits at out[it], |d|'s at out[40 + it], it = W-1
    (popped first, read unsigned: & 15) down to 0; the rest stay zero.

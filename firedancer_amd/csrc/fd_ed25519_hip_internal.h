@@ -39,7 +39,9 @@ extern "C" {
 #define FD_ED25519_BTABC_BITS     16
 #define FD_ED25519_BTABC_ENTRIES  (1 << FD_ED25519_BTABC_BITS)
 
-/* Per-lane tables [1..8](-A) and [1..8](-+R) in cached form, in HBM: 2 x 8
+/* Per-lane tables in cached form, in HBM -- the half-size form's joint
+   table a (-A) + r (-+R) (12 slots, fd_ed25519_kernels.hip), sized as the
+   two tables [1..8](-A) and [1..8](-+R) it replaced: 2 x 8
    entries x 40 int32 per lane, laid out [wave][lane][entry][quad] (int4
    granules, lane stride 160 int4): a lookup
    reads 160 contiguous bytes of the lane's own table, so every fetched line

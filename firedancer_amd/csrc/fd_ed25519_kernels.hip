@@ -18,15 +18,16 @@
    point.  Step 5 runs, for all but ~1e-6 of signatures, in the half-size
    form: with c == d k (mod 8L), d odd (the scalar kernel, fd25519_half.h,
    every pair re-checked with integers only), [c](-A) + [|d|](-+R) +
-   [s_lo]B + [s_hi][2^144]B == 0 in a four-scalar Straus loop of 33 signed
-   4-bit windows (dsm_half_one), exactly equivalent since [d] is invertible
+   [s_lo]B + [s_hi][2^144]B == 0 in a four-scalar Straus loop of 66 signed
+   2-bit windows (dsm_half_one), exactly equivalent since [d] is invertible
    on the group of order 8L; the rest in the full-length form
    [k](-A) + [S]B == R (dsm_full_one).  Fixed windows instead of the
    reference's sliding wNAF make every lane of a wave execute the same
    additions; the group element is the same, so the verdict is
    bit-identical.
 
-   Tables: per-lane [1..8](-A) and [1..8](-+R) in an HBM scratch of the
+   Tables: per-lane a (-A) + r (-+R), a in [0, 2], r in [-2, 2] (11 entries;
+   [0..8](-A) for the full-length form) in an HBM scratch of the
    persistent dsm grid (dynamically scheduled, 64 items per wave); the base
    tables [0..2^24)B and [0..2^24)[2^144]B (or the compact radix-2^16 pair)
    and [0..2^15]B (full-length form) in HBM, shared by the engines of a
@@ -274,8 +275,8 @@ FD_DEV void table_store(int4* tab, int e, ge_cached c) {
 }
 
 /* The cached identity (Y+X = Y-X = 1, 2Z = 2, T = 0) that a zero digit
-   reads from the half-size form's [1..8] lane tables: one 160-byte
-   entry shared by every lane, L2-resident. */
+   pair reads instead of an entry of the half-size form's lane table: one
+   160-byte entry shared by every lane, L2-resident. */
 __device__ const int4 fd_ident_cached[10] = {{1, 0, 0, 0}, {0, 0, 0, 0}, {0, 0, 1, 0}, {0, 0, 0, 0}, {0, 0, 0, 0},
                                              {2, 0, 0, 0}, {0, 0, 0, 0}, {0, 0, 0, 0}, {0, 0, 0, 0}, {0, 0, 0, 0}};
 
@@ -565,48 +566,154 @@ struct fd_bw {
        [c](-A) + [|d|](-sign(d) R) + [s_lo]B + [s_hi]B' == 0,   B' = [2^144]B
 
    exactly equivalent (fd25519_half.h: the group has order 8L and [d] is
-   invertible on it).  A four-scalar Straus loop over W signed 4-bit
-   windows, W = 33 unless a lane of the wave has |d| >= 2^131 (~0.16% of
-   signatures; then up to 38, the same W for the whole wave, the other
-   lanes' top digits being 0): 4(W-1) = 128 doublings (against 252 for the
-   reference's double-scalar form), W additions from each lane's
-   [1..8](-A) and [1..8](-+R) tables (a zero digit adds the shared identity entry)
-   (HBM, lane-contiguous 160-byte entries) and 6 + 5 mixed additions from
-   the two unsigned radix-2^24 base tables [0..2^24)B and [0..2^24)B'
-   (2 GiB each, HBM) -- or, with BW = 16, 9 + 7 from the compact
-   [0..2^16) tables (8 MiB each).  Every table entry is loaded
-   one step ahead of its use: the -A entry before the window's doublings,
-   the R entry before the -A addition, the base entries before the R
-   addition.  The result is compared with the identity (X == 0, Y == Z). */
+   invertible on it).  A four-scalar Straus loop: c and |d| in W signed
+   2-bit windows (digits in [-2, 1], the top ones in [0, 2]), W = 66 unless
+   a lane of the wave has |d| >= 2^131 (~0.16% of signatures; then up to
+   76, the same W for the whole wave, the other lanes' top digits being 0):
+   2(W-1) = 130 doublings (against 252 for the reference's double-scalar
+   form) and ONE addition per window from the lane's joint table of
+   a A' + r R', A' = -A, R' = -sign(d) R (HBM, lane-contiguous 160-byte
+   entries), and 6 + 5 mixed additions from the two unsigned radix-2^24
+   base tables [0..2^24)B and [0..2^24)B' (2 GiB each, HBM) -- or, with
+   BW = 16, 9 + 7 from the compact [0..2^16) tables (8 MiB each) -- at the
+   even windows 2i where the 4-bit window i of s_lo / s_hi starts a digit.
+   The window's table entry and base entries are loaded before its
+   doublings.  The result is compared with the identity (X == 0, Y == Z).
+
+   The joint table.  A digit pair (a, r) is taken up to a common sign
+   s = (a < 0 or (a == 0 and r < 0)): classes (a', r') with a' in {0, 1, 2},
+   r' in [-2, 2], without (0, <= 0): slot 5 a' + r' - 1 in 0..11; (0, 0)
+   reads the shared identity entry, and the entry is negated for s (free:
+   ge_cached_cneg).  (2, -2) needs a digit +2, which only the top window
+   has, and there both digits are >= 0: slot 7 is never read and not built
+   (tests/test_dsm_joint_model.py enumerates the classes).  11 entries,
+   1760 B written per signature, 71 products and 8 squarings to build
+   (two 8-entry tables: 2560 B, 116 products); the loop costs what two
+   additions per 4-bit window did (2 x (8S + 3 + 4M + 4M + 3M)), and holds
+   one prefetched entry instead of two (interleaved A/B x3 against the two
+   tables: dsm -1.7%, profiles/dsm_joint_table_ab.txt).
+
+   Entry bounds.  A' and R' are table_build's first entry (Y+X, Y-X of a
+   centered 1x X and a [0, 2x) Y: within [-1x, 3x]; 2Z = 2; -2dT a
+   product).  Every other entry is ge_p3_to_cached<true> of a
+   ge_p1p1_to_p3_uxyt output, exactly as table_build's [2..8]: Y+X-p, Y-X
+   in [-2x, 2x], 2Z <= 2.02x, -+2dT within 2x.  What is new is what is
+   converted: the doubling of an affine point (inputs 1x, 2x, 1: within
+   ge_p2_dbl's 2x; its completed point has X, Z, T within 3x, Y in
+   [-1x, 3x]) and mixed additions whose left operand is an entry read back
+   (jtab_step): the 19-sides are the affine point's y+x, y-x (<= 3.03x)
+   and T (centered); the entry's Y+X, Y-X (either bound above) are
+   19-free, 2Z +- a centered product is within 3.03x, so the completed
+   point has ge_madd's bounds. */
+
+/* the cached entry of P (X, Y, T unsigned, Z centered), or of -P, with -2dT */
+FD_DEV void jtab_store(int4* tab, int slot, const ge_p3& P, bool neg) {
+  ge_cached c;
+  ge_p3_to_cached<true>(c, P);
+  fe_neg(c.T2d, c.T2d);
+  ge_cached_cneg(c, neg);
+  atab_store(tab, slot, c);
+}
+
+/* the affine point (+-x, y) of A (which = 0) or R */
+FD_DEV void jtab_affine(ge_p3& P, const fd_ed25519_verify_params_t& p, int which, uint64_t j, bool negate) {
+  fe x, xn;
+  load_pt(x, P.Y, p, which, j);
+  fe_neg(xn, x);
+  fe_select(P.X, x, xn, negate);
+  fe_1(P.Z);
+  fe_mul(P.T, P.X, P.Y);
+}
+
+/* One step of the build: E = the entry at src (Y+X, Y-X, 2Z, -2dT), q
+   affine: E + q into slot sp and E - q (mneg: its negative) into slot sm
+   (sm < 0: not built).  ge_madd with its left operand read back from the
+   table -- the entry's Y+X, Y-X and 2Z are the sums ge_madd forms, and
+   m = (-2d T1)(x2 y2) is its -c -- the two results sharing m; E - q is
+   E + (-q): q's y+x and y-x exchanged, m negated. */
+FD_DEV void jtab_step(int4* tab, int src, const ge_p3& q, int sp, int sm, bool mneg) {
+  ge_cached e;
+  atab_load(e, tab, src);
+  fe qs, qd, m;
+  fe_add(qs, q.Y, q.X);
+  fe_sub(qd, q.Y, q.X);
+  fe_mul(m, e.T2d, q.T);
+#pragma clang loop unroll(disable)
+  for (int h = sm < 0 ? 1 : 0; h < 2; h++) {
+    const bool plus = h != 0;
+    fe u, v, a, b, ms, mn;
+    fe_select(u, qd, qs, plus);
+    fe_select(v, qs, qd, plus);
+    fe_mul_u(a, e.YplusX, u);
+    fe_mul_u(b, e.YminusX, v);
+    fe_neg(mn, m);
+    fe_select(ms, mn, m, plus);
+    ge_p1p1 sum;
+    fe_sub(sum.X, a, b);
+    fe_add(sum.Y, a, b);
+    fe_sub(sum.Z, e.Z2, ms);
+    fe_add(sum.T, e.Z2, ms);
+    ge_p3 K;
+    ge_p1p1_to_p3_uxyt(K, sum);
+    jtab_store(tab, plus ? sp : sm, K, !plus && mneg);
+  }
+}
+
+/* A', 2A', R', 2R' from the points, then four steps from the entries
+   written so far (a lane reads back its own stores): rolled, so that each
+   body holds one point and one entry -- built straight-line, with the
+   points and their precomp forms held across the steps, the kernel
+   spilled 15-25 VGPRs; so it does not, and needs no scratch at all */
+#define FD_JSLOT(a, r) (5 * (a) + (r) - 1)
+FD_DEV void joint_table_build(int4* tab, const fd_ed25519_verify_params_t& p, uint64_t j, bool rneg) {
+  ge_p3 P;
+#pragma clang loop unroll(disable)
+  for (int w = 0; w < 2; w++) {
+    jtab_affine(P, p, w, j, w ? rneg : true);
+    ge_cached c1;
+    ge_p3_to_cached(c1, P);
+    table_store<true>(tab, w ? FD_JSLOT(0, 1) : FD_JSLOT(1, 0), c1);
+    ge_p1p1 sum;
+    ge_p3_dbl(sum, P);
+    ge_p3 D;
+    ge_p1p1_to_p3_uxyt(D, sum);
+    jtab_store(tab, w ? FD_JSLOT(0, 2) : FD_JSLOT(2, 0), D, false);
+  }
+#pragma clang loop unroll(disable)
+  for (int st = 0; st < 4; st++) {
+    /* 2R' +- A' (the difference stored as A' - 2R'), A' +- R', 2A' +- R', (2A' + R') + R' */
+    const int src = st == 0 ? FD_JSLOT(0, 2) : st == 1 ? FD_JSLOT(1, 0) : st == 2 ? FD_JSLOT(2, 0) : FD_JSLOT(2, 1);
+    const int sp = st == 0 ? FD_JSLOT(1, 2) : st == 1 ? FD_JSLOT(1, 1) : st == 2 ? FD_JSLOT(2, 1) : FD_JSLOT(2, 2);
+    const int sm = st == 0 ? FD_JSLOT(1, -2) : st == 1 ? FD_JSLOT(1, -1) : st == 2 ? FD_JSLOT(2, -1) : -1;
+    jtab_affine(P, p, st ? 1 : 0, j, st ? rneg : true);
+    jtab_step(tab, src, P, sp, sm, st == 0);
+  }
+}
+
+/* the entry of the digit pair (a, r) after the common sign: a in [0, 2] */
+FD_DEV const int4* jtab_entry(const int4* tab, int a, int r) {
+  const int slot = FD_JSLOT(a, r);
+  return slot < 0 ? fd_ident_cached : tab + slot * 10;
+}
 
 template <int BW>
-FD_DEV int dsm_half_one(const fd_ed25519_verify_params_t& p, uint64_t j, int4* tabA, int4* tabR) {
+FD_DEV int dsm_half_one(const fd_ed25519_verify_params_t& p, uint64_t j, int4* tab) {
   int code = precheck(p, j);
   const uint32_t hf = p.hflag[j];
-
-  /* lane tables: [1..8](-A) and [1..8](-sign(d) R) */
-  {
-    fe x, y;
-    load_pt(x, y, p, 0, j);
-    table_build<true, true>(tabA, x, y, true);
-    load_pt(x, y, p, 1, j);
-    table_build<true, true>(tabR, x, y, !(hf & FD_HF_DNEG));
-  }
-  /* digits, most significant first, top-aligned in 160 bits: c, |d| in
-     radix 16 (W signed digits, the top one in [0,8]), s_lo, s_hi in
-     radix 2^24 (6 and 5 unsigned digits: no recoding, no negation) */
+  joint_table_build(tab, p, j, !(hf & FD_HF_DNEG));
+  /* c, |d| in radix 4: W signed digits in [-2, 1], the top one in [0, 2] */
   uint32_t cd[5], dd[5], ld[5], hd[5];
-  int W = 33;
+  int W = 66;
   {
     uint32_t x[5], t[5];
     load_hs(x, p, 5, 5, j);
-    /* windows this lane needs: |d| < 2^(4W-1); the wave takes the max */
-    const int wl = (fd_half_bitlen<5>(x) + 4) >> 2;
+    /* windows this lane needs: |d| < 2^(2W-1); the wave takes the max */
+    const int wl = (fd_half_bitlen<5>(x) + 2) >> 1;
 #pragma unroll
-    for (int w = 34; w <= (FD_HALF_DBITS_MAX + 4) / 4; w++) W += __ballot(wl >= w) != 0ull;
-    const int sh = 160 - 4 * W;
-    shl160v(t, x, sh); recode160<4>(dd, t);
-    load_hs(x, p, 0, 5, j);  shl160v(t, x, sh); recode160<4>(cd, t);
+    for (int w = 67; w <= (FD_HALF_DBITS_MAX + 2) / 2; w++) W += __ballot(wl >= w) != 0ull;
+    const int sh = 160 - 2 * W;
+    shl160v(t, x, sh); recode160<2>(dd, t);
+    load_hs(x, p, 0, 5, j);  shl160v(t, x, sh); recode160<2>(cd, t);
     load_hs(x, p, 10, 5, j); shl160<fd_bw<BW>::LO_SHL>(ld, x);
     load_hs(x, p, 15, 4, j); shl160<fd_bw<BW>::HI_SHL>(hd, x);
   }
@@ -614,33 +721,41 @@ FD_DEV int dsm_half_one(const fd_ed25519_verify_params_t& p, uint64_t j, int4* t
   const int4* g_btab2 = reinterpret_cast<const int4*>(p.btab_hi);
 
   ge_p3 P;
-  ge_p3_0(P);
   ge_p1p1 Rt;
   ge_p2 Q;
+  {
+    /* the top window (no base digit there, both digits >= 0): the sum is
+       the entry itself, 2X = (Y+X) - (Y-X), 2Y = (Y+X) + (Y-X), 2Z as
+       stored -- no T: a doubling follows.  The sums reach 4x and the
+       doubling takes 2x, so they are carried. */
+    const int ea = pop160<2>(cd) & 3, er = pop160<2>(dd) & 3;
+    ge_cached cj;
+    atab_load(cj, jtab_entry(tab, ea, er), 0);
+    fe t;
+    fe_sub(t, cj.YplusX, cj.YminusX);
+    fe_carry(Q.X, t);
+    fe_add(t, cj.YplusX, cj.YminusX);
+    fe_carry(Q.Y, t);
+    Q.Z = cj.Z2;
+  }
 #pragma clang loop unroll(disable)
-  for (int it = W - 1; it >= 0; it--) {
-    int ea = pop160<4>(cd), er = pop160<4>(dd);
-    if (it == W - 1) { ea &= 15; er &= 15; }   /* top digits in [0,8] */
-    ge_cached ca, cr;
-    const bool blo = fd_bw<BW>::lo_at(it), bhi = fd_bw<BW>::hi_at(it);
+  for (int it = W - 2; it >= 0; it--) {
+    const int ea = pop160<2>(cd), er = pop160<2>(dd);
+    const bool sg = ea < 0 || (ea == 0 && er < 0);
+    ge_cached cj;
+    const bool blo = !(it & 1) && fd_bw<BW>::lo_at(it >> 1), bhi = !(it & 1) && fd_bw<BW>::hi_at(it >> 1);
     ge_precomp b1, b2;
-    atab_load(ca, tab_entry<true>(tabA, ea), 0);
-    if (it != W - 1) {
-#pragma clang loop unroll(disable)
-      for (int dbl = 0; dbl < 4; dbl++) {
-        ge_p2_dbl(Rt, Q);
-        if (dbl < 3) ge_p1p1_to_p2(Q, Rt);
-      }
-      ge_p1p1_to_p3_u(P, Rt);
-    }
-    atab_load(cr, tab_entry<true>(tabR, er), 0);
-    ge_cached_cneg(ca, ea < 0);
-    ge_add<true>(Rt, P, ca);
-    ge_p1p1_to_p3_u(P, Rt);
+    atab_load(cj, jtab_entry(tab, sg ? -ea : ea, sg ? -er : er), 0);
     if (blo) btab16_load(b1, g_btab, (int)pop160u<BW>(ld));
     if (bhi) btab16_load(b2, g_btab2, (int)pop160u<BW>(hd));
-    ge_cached_cneg(cr, er < 0);
-    ge_add<true>(Rt, P, cr);
+#pragma clang loop unroll(disable)
+    for (int dbl = 0; dbl < 2; dbl++) {
+      ge_p2_dbl(Rt, Q);
+      if (dbl < 1) ge_p1p1_to_p2(Q, Rt);
+    }
+    ge_p1p1_to_p3_u(P, Rt);
+    ge_cached_cneg(cj, sg);
+    ge_add<true>(Rt, P, cj);
     if (blo) {
       ge_p1p1_to_p3_uxyt(P, Rt);
       ge_madd(Rt, P, b1);
@@ -822,8 +937,9 @@ fd_ed25519_dsm_kernel(fd_ed25519_verify_params_t p) {
   const uint64_t wave = ((uint64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
   int4* tabA = reinterpret_cast<int4*>(static_cast<char*>(p.atab) + wave * FD_ED25519_ATAB_BYTES_PER_WAVE) +
                lane * (2 * FD_ED25519_ATAB_STRIDE * 10);
-  int4* tabR = tabA + FD_ED25519_ATAB_STRIDE * 10;   /* the full-length form uses tabA's 9 entries, into tabR's space */
+  /* a lane's space is two 8-entry tables: the joint table's 11 entries, or the full-length form's 9 */
 #if FD_ED25519_AB_LDS_BASE
+  int4* tabR = tabA + FD_ED25519_ATAB_STRIDE * 10;
   __shared__ int4 s_b8[2 * 256 * (FD_ED25519_BTAB16_STRIDE / 4)];
   {
     const int4* g_lo = reinterpret_cast<const int4*>(p.btab8_lo);
@@ -859,7 +975,7 @@ fd_ed25519_dsm_kernel(fd_ed25519_verify_params_t p) {
       if (!(p.hflag[j] & FD_HF_FULL))
         p.out[p.base + j] = (int8_t)dsm_half_one_lds(p, j, tabA, tabR, s_b8, s_b8 + 256 * (FD_ED25519_BTAB16_STRIDE / 4));
 #else
-      if (!(p.hflag[j] & FD_HF_FULL)) p.out[p.base + j] = (int8_t)dsm_half_one<BW>(p, j, tabA, tabR);
+      if (!(p.hflag[j] & FD_HF_FULL)) p.out[p.base + j] = (int8_t)dsm_half_one<BW>(p, j, tabA);
 #endif
     }
   }
