@@ -415,6 +415,47 @@ int fd_ed25519_hip_launch_txn_finish( int8_t const * d_sig_codes, uint32_t const
                                       uint32_t const * d_txn_cnt, uint8_t const * d_parse_ok, int8_t * d_txn_out,
                                       uint64_t ntxn, void * stream );
 
+/* ---- Ed25519 precompile instructions (fd_ed25519_txn.hip) ---- */
+
+/* stage: one lane per transaction parses the payload, walks its Ed25519
+   precompile instructions (fd_precompile_core.h) and fills the slots
+   [ent_first[t], ent_first[t+1]) -- never one outside them */
+typedef struct {
+  uint8_t const *  payloads;   /* payload bytes, readable 16 B past each    */
+  uint64_t const * pay_off;    /* [ntxn]                                    */
+  uint32_t const * pay_sz;     /* [ntxn]                                    */
+  uint32_t const * ent_first;  /* [ntxn+1] the caller's reservation          */
+  uint64_t         ntxn;
+  uint64_t         n_ent;      /* slots in all                               */
+  uint8_t *        sigs;       /* [n_ent][64] out, 16-B aligned              */
+  uint8_t *        pubs;       /* [n_ent][32] out, 16-B aligned              */
+  uint64_t *       msg_off;    /* [n_ent] out: into payloads                  */
+  uint32_t *       msg_sz;     /* [n_ent] out                                 */
+  int8_t *         pre;        /* [n_ent] out: 0, DATA_OFFSET, or the transaction's status */
+  uint8_t *        ent_instr;  /* [n_ent] out: the listing instruction's index */
+  int8_t *         status;     /* [ntxn] out: 0, PARSE_FAILED, BAD_RESERVATION */
+  uint8_t *        hdr_instr;  /* [ntxn] out: first instruction whose header fails (0xFF: none) */
+  uint8_t *        hdr_pos;    /* [ntxn] out: entries ahead of it             */
+} fd_ed25519_precompile_stage_params_t;
+
+typedef struct {
+  int8_t const *   codes;      /* [n_ent] the verify phases' codes           */
+  int8_t const *   pre;
+  uint8_t const *  ent_instr;
+  int8_t const *   status;
+  uint8_t const *  hdr_instr;
+  uint8_t const *  hdr_pos;
+  uint32_t const * ent_first;
+  uint64_t         ntxn;
+  uint64_t         n_ent;
+  int8_t *         txn_out;    /* [ntxn]                                     */
+  uint8_t *        instr_out;  /* [ntxn]                                     */
+  int8_t *         ent_out;    /* [n_ent] or NULL                            */
+} fd_ed25519_precompile_finish_params_t;
+
+int fd_ed25519_hip_launch_precompile_stage( fd_ed25519_precompile_stage_params_t const * p, void * stream );
+int fd_ed25519_hip_launch_precompile_finish( fd_ed25519_precompile_finish_params_t const * p, void * stream );
+
 /* ---- generator (fd_ed25519_gen.hip) ---- */
 
 typedef struct {

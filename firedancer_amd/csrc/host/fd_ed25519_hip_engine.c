@@ -19,7 +19,10 @@
 
 #define _GNU_SOURCE
 #include "../../../include/fd_ed25519_hip.h"
+#include "../../../include/fd_ed25519_hip_tile.h"   /* fd_ed25519_hip_txn_t, for the parse core */
 #include "../fd_ed25519_hip_internal.h"
+#include "../fd_txn_parse_core.h"
+#include "../fd_precompile_core.h"
 
 #include <hip/hip_runtime_api.h>
 #include <pthread.h>
@@ -93,6 +96,13 @@ struct fd_ed25519_hip_engine {
   uint32_t *   h_tfirst; uint32_t * d_tfirst;
   uint32_t *   h_tcnt;  uint32_t * d_tcnt;
   int8_t *     h_tout;  int8_t *   d_tout;
+  /* precompile_host: the per-transaction inputs (pay_off, ent_first, pay_sz)
+     and outputs (txn_out, instr_out) in one block each, and the device
+     workspace of precompile_dev */
+  uint64_t     pc_in_cap, pc_out_cap, pc_work_cap;   /* bytes */
+  uint8_t *    h_pc_in;  uint8_t *  d_pc_in;
+  uint8_t *    h_pc_out; uint8_t *  d_pc_out;
+  uint8_t *    d_pc_work;
 
   /* per-phase event timing (bench / profiling) */
   int          timing;
@@ -380,6 +390,8 @@ engine_free( fd_ed25519_hip_engine_t * e ) {
   hipHostFree( e->h_msgs ); hipHostFree( e->h_off ); hipHostFree( e->h_sz ); hipHostFree( e->h_sigs );
   hipHostFree( e->h_pubs ); hipHostFree( e->h_out ); hipHostFree( e->h_tfirst ); hipHostFree( e->h_tcnt );
   hipHostFree( e->h_tout );
+  hipFree( e->d_pc_in ); hipFree( e->d_pc_out ); hipFree( e->d_pc_work );
+  hipHostFree( e->h_pc_in ); hipHostFree( e->h_pc_out );
   if( e->tm_ev_init )
     for( int i=0; i<FD_ED25519_HIP_TIMING_MAX; i++ )
       for( int j=0; j<=FD_ED25519_PHASE_CNT; j++ ) hipEventDestroy( e->tm_ev[i][j] );
@@ -1326,6 +1338,153 @@ fd_ed25519_hip_verify_txns_host( fd_ed25519_hip_engine_t * e, unsigned long ntxn
         out_sig[ txn_first[t] + j ] = (cnt>=1U && cnt<=16U) ? e->h_out[ e->h_tfirst[t] + j ] : (signed char)FD_ED25519_ERR_SIG;
     }
   }
+  return FD_ED25519_HIP_OK;
+}
+
+/* ---- Ed25519 precompile instructions (include/fd_ed25519_hip.h Part 2b) -- */
+
+_Static_assert( FD_ED25519_HIP_PRECOMPILE_ENT_MAX==FD_PRECOMPILE_CORE_ENT_MAX, "entry bound" );
+_Static_assert( FD_ED25519_HIP_PRECOMPILE_ERR_SIGNATURE==FD_PRECOMPILE_CORE_ERR_SIGNATURE &&
+                FD_ED25519_HIP_PRECOMPILE_ERR_DATA_OFFSET==FD_PRECOMPILE_CORE_ERR_DATA_OFFSET &&
+                FD_ED25519_HIP_PRECOMPILE_ERR_INSTR_DATA_SIZE==FD_PRECOMPILE_CORE_ERR_INSTR_DATA_SIZE,
+                "public and core precompile codes differ" );
+/* the plan's entries are the core's, copied as bytes */
+_Static_assert( sizeof(fd_ed25519_hip_precompile_ent_t)==sizeof(fd_precompile_core_ent_t) &&
+                offsetof(fd_ed25519_hip_precompile_ent_t,pre    )==offsetof(fd_precompile_core_ent_t,pre    ) &&
+                offsetof(fd_ed25519_hip_precompile_ent_t,sig_off)==offsetof(fd_precompile_core_ent_t,sig_off) &&
+                offsetof(fd_ed25519_hip_precompile_ent_t,pub_off)==offsetof(fd_precompile_core_ent_t,pub_off) &&
+                offsetof(fd_ed25519_hip_precompile_ent_t,msg_off)==offsetof(fd_precompile_core_ent_t,msg_off) &&
+                offsetof(fd_ed25519_hip_precompile_ent_t,msg_sz )==offsetof(fd_precompile_core_ent_t,msg_sz ),
+                "plan entry layout" );
+
+/* count and plan: the walk the stage kernel runs, on the host (no GPU) */
+unsigned
+fd_ed25519_hip_precompile_count( unsigned char const * payload, unsigned long payload_sz ) {
+  fd_precompile_core_sum_t sum;
+  int parsed;
+  fd_precompile_core_plan( payload, payload_sz, NULL, 0UL, &sum, &parsed );
+  return sum.ent_cnt;
+}
+
+int
+fd_ed25519_hip_precompile_plan( unsigned char const * payload, unsigned long payload_sz,
+                                fd_ed25519_hip_precompile_ent_t * ents, unsigned long cap,
+                                signed char * parse_or_header_code, unsigned char * instr ) {
+  fd_precompile_core_sum_t sum;
+  int parsed;
+  int n = fd_precompile_core_plan( payload, payload_sz, (fd_precompile_core_ent_t *)ents, ents ? cap : 0UL, &sum, &parsed );
+  if( parse_or_header_code )
+    *parse_or_header_code = (signed char)( !parsed ? FD_ED25519_HIP_PRECOMPILE_PARSE_FAILED
+                                         : sum.hdr_instr!=0xFF ? FD_ED25519_HIP_PRECOMPILE_ERR_INSTR_DATA_SIZE : 0 );
+  if( instr ) *instr = sum.hdr_instr;
+  return n;
+}
+
+int
+fd_ed25519_hip_precompile_dev( fd_ed25519_hip_engine_t * e, unsigned long ntxn, unsigned char const * payloads,
+                               unsigned long const * pay_off, unsigned int const * pay_sz,
+                               unsigned int const * ent_first, unsigned long n_ent, void * work,
+                               signed char * txn_out, unsigned char * instr_out, signed char * ent_out,
+                               void * stream ) {
+  if( !e ) return FD_ED25519_HIP_ERR_INVAL;
+  if( !ntxn ) return FD_ED25519_HIP_OK;
+  if( !payloads || !pay_off || !pay_sz || !ent_first || !work || !txn_out || !instr_out ||
+      n_ent>ntxn*FD_ED25519_HIP_PRECOMPILE_ENT_MAX ) return FD_ED25519_HIP_ERR_INVAL;
+  if( (uintptr_t)work & 15UL ) {
+    snprintf( fd_ed25519_hip_errbuf, sizeof(fd_ed25519_hip_errbuf), "precompile work must be 16-byte aligned" );
+    return FD_ED25519_HIP_ERR_INVAL;
+  }
+  hipStream_t st = stream ? (hipStream_t)stream : e->stream;
+  HIPCHK( hipSetDevice( e->device ), "hipSetDevice" );
+  /* FD_ED25519_HIP_PRECOMPILE_WORK_BYTES: [n_ent] sigs 64, pubs 32, msg_off
+     8, msg_sz 4, codes, pre, ent_instr 1 each; [ntxn] status, hdr_instr,
+     hdr_pos (every array aligned to its element at any n_ent) */
+  uint8_t * w = (uint8_t *)work;
+  fd_ed25519_precompile_stage_params_t sp;
+  memset( &sp, 0, sizeof(sp) );
+  sp.payloads = payloads; sp.pay_off = (uint64_t const *)pay_off; sp.pay_sz = pay_sz; sp.ent_first = ent_first;
+  sp.ntxn = ntxn; sp.n_ent = n_ent;
+  sp.sigs      = w;
+  sp.pubs      = w +  64UL*n_ent;
+  sp.msg_off   = (uint64_t *)( w +  96UL*n_ent );
+  sp.msg_sz    = (uint32_t *)( w + 104UL*n_ent );
+  int8_t * codes = (int8_t *)( w + 108UL*n_ent );
+  sp.pre       = (int8_t *)( w + 109UL*n_ent );
+  sp.ent_instr = w + 110UL*n_ent;
+  sp.status    = (int8_t *)( w + 111UL*n_ent );
+  sp.hdr_instr = w + 111UL*n_ent + ntxn;
+  sp.hdr_pos   = w + 111UL*n_ent + 2UL*ntxn;
+  int err = fd_ed25519_hip_launch_precompile_stage( &sp, st );
+  if( err ) return hip_fail( (hipError_t)err, "precompile_stage launch" );
+  if( n_ent ) {
+    err = verify_common( e, n_ent, payloads, (unsigned long const *)sp.msg_off, sp.msg_sz, NULL, sp.sigs, sp.pubs,
+                         (signed char *)codes, st );
+    if( err ) return err;
+  }
+  fd_ed25519_precompile_finish_params_t fp;
+  memset( &fp, 0, sizeof(fp) );
+  fp.codes = codes; fp.pre = sp.pre; fp.ent_instr = sp.ent_instr; fp.status = sp.status;
+  fp.hdr_instr = sp.hdr_instr; fp.hdr_pos = sp.hdr_pos; fp.ent_first = ent_first; fp.ntxn = ntxn; fp.n_ent = n_ent;
+  fp.txn_out = (int8_t *)txn_out; fp.instr_out = instr_out; fp.ent_out = (int8_t *)ent_out;
+  err = fd_ed25519_hip_launch_precompile_finish( &fp, st );
+  if( err ) return hip_fail( (hipError_t)err, "precompile_finish launch" );
+  return FD_ED25519_HIP_OK;
+}
+
+/* device-only buffer grown on demand, like grow_pair */
+static int
+grow_dev( uint8_t ** d, uint64_t * cap, uint64_t need ) {
+  if( need<=*cap ) return FD_ED25519_HIP_OK;
+  uint64_t ncap = *cap ? *cap : 4096UL;
+  while( ncap<need ) ncap *= 2UL;
+  hipFree( *d ); *d = NULL; *cap = 0UL;
+  HIPCHK( hipMalloc( (void **)d, ncap ), "hipMalloc" );
+  *cap = ncap;
+  return FD_ED25519_HIP_OK;
+}
+
+int
+fd_ed25519_hip_precompile_host( fd_ed25519_hip_engine_t * e, unsigned long ntxn, unsigned char const * payloads,
+                                unsigned long const * pay_off, unsigned int const * pay_sz, signed char * txn_out,
+                                unsigned char * instr_out ) {
+  if( !e ) return FD_ED25519_HIP_ERR_INVAL;
+  if( !ntxn ) return FD_ED25519_HIP_OK;
+  if( !payloads || !pay_off || !pay_sz || !txn_out || !instr_out ) return FD_ED25519_HIP_ERR_INVAL;
+  HIPCHK( hipSetDevice( e->device ), "hipSetDevice" );
+  uint64_t bytes = 0UL;
+  for( uint64_t t=0UL; t<ntxn; t++ ) bytes += pay_sz[t];
+  /* in: pay_off u64 [ntxn], ent_first u32 [ntxn+1], pay_sz u32 [ntxn]; out: txn_out, instr_out [ntxn] */
+  uint64_t in_bytes = 16UL*ntxn + 4UL;
+  int err;
+  if( (err = stage_msgs( e, bytes )) ) return err;   /* 64 bytes of room behind the last payload */
+  if( (err = grow_pair( (void **)&e->h_pc_in,  (void **)&e->d_pc_in,  &e->pc_in_cap,  in_bytes,  1UL )) ) return err;
+  if( (err = grow_pair( (void **)&e->h_pc_out, (void **)&e->d_pc_out, &e->pc_out_cap, 2UL*ntxn, 1UL )) ) return err;
+  uint64_t * h_off   = (uint64_t *)e->h_pc_in;
+  uint32_t * h_first = (uint32_t *)( e->h_pc_in + 8UL*ntxn );
+  uint32_t * h_sz    = h_first + ntxn + 1UL;
+  uint64_t pos = 0UL, n_ent = 0UL;
+  for( uint64_t t=0UL; t<ntxn; t++ ) {
+    if( pay_sz[t] ) memcpy( e->h_msgs + pos, payloads + pay_off[t], pay_sz[t] );
+    h_off  [t] = pos;
+    h_sz   [t] = pay_sz[t];
+    h_first[t] = (uint32_t)n_ent;
+    n_ent += fd_ed25519_hip_precompile_count( e->h_msgs + pos, pay_sz[t] );   /* of the copy the device will read */
+    pos   += pay_sz[t];
+  }
+  h_first[ntxn] = (uint32_t)n_ent;
+  if( (err = grow_dev( &e->d_pc_work, &e->pc_work_cap, FD_ED25519_HIP_PRECOMPILE_WORK_BYTES( ntxn, n_ent ) )) ) return err;
+  hipStream_t st = e->stream;
+  HIPCHK( hipMemcpyAsync( e->d_msgs, e->h_msgs, bytes ? bytes : 1UL, hipMemcpyHostToDevice, st ), "H2D payloads" );
+  HIPCHK( hipMemcpyAsync( e->d_pc_in, e->h_pc_in, in_bytes, hipMemcpyHostToDevice, st ), "H2D precompile in" );
+  uint8_t * d_out = e->d_pc_out;
+  if( (err = fd_ed25519_hip_precompile_dev( e, ntxn, e->d_msgs, (unsigned long const *)e->d_pc_in,
+                                            (unsigned int const *)( e->d_pc_in + 8UL*ntxn ) + ntxn + 1UL,
+                                            (unsigned int const *)( e->d_pc_in + 8UL*ntxn ), n_ent, e->d_pc_work,
+                                            (signed char *)d_out, d_out + ntxn, NULL, st )) ) return err;
+  HIPCHK( hipMemcpyAsync( e->h_pc_out, d_out, 2UL*ntxn, hipMemcpyDeviceToHost, st ), "D2H precompile out" );
+  HIPCHK( hipStreamSynchronize( st ), "precompile" );
+  memcpy( txn_out,   e->h_pc_out,        ntxn );
+  memcpy( instr_out, e->h_pc_out + ntxn, ntxn );
   return FD_ED25519_HIP_OK;
 }
 

@@ -91,6 +91,47 @@ _lib.fd_ed25519_hip_private_diag_dsm_nmax.restype = ctypes.c_ulong
 _lib.fd_ed25519_hip_private_diag_dsm_check.argtypes = [ctypes.c_int, ctypes.c_ulong, ctypes.c_ulong, ctypes.c_int] + [_u8p] * 7
 _lib.fd_ed25519_hip_strerror.argtypes = [ctypes.c_int]
 _lib.fd_ed25519_hip_strerror.restype = ctypes.c_char_p
+
+# Ed25519 precompile instructions of raw transactions (include/fd_ed25519_hip.h Part 2b)
+PRECOMPILE_ERR_SIGNATURE = -3        # FD_EXECUTOR_PRECOMPILE_ERR_SIGNATURE
+PRECOMPILE_ERR_DATA_OFFSET = -4      # FD_EXECUTOR_PRECOMPILE_ERR_DATA_OFFSET
+PRECOMPILE_ERR_INSTR_DATA_SIZE = -5  # FD_EXECUTOR_PRECOMPILE_ERR_INSTR_DATA_SIZE
+PRECOMPILE_PARSE_FAILED = -16
+PRECOMPILE_BAD_RESERVATION = -17
+PRECOMPILE_ENT_MAX = 87
+# fd_ed25519_hip_precompile_ent_t
+PRECOMPILE_ENT_DTYPE = np.dtype([("instr", np.uint8), ("pre", np.int8), ("sig_off", np.uint16), ("pub_off", np.uint16),
+                                 ("msg_off", np.uint16), ("msg_sz", np.uint16)])
+_lib.fd_ed25519_hip_precompile_count.argtypes = [ctypes.c_char_p, ctypes.c_ulong]
+_lib.fd_ed25519_hip_precompile_count.restype = ctypes.c_uint
+_lib.fd_ed25519_hip_precompile_plan.argtypes = [ctypes.c_char_p, ctypes.c_ulong, ctypes.c_void_p, ctypes.c_ulong,
+                                                ctypes.POINTER(ctypes.c_byte), ctypes.POINTER(ctypes.c_ubyte)]
+_lib.fd_ed25519_hip_precompile_dev.argtypes = [ctypes.c_void_p, ctypes.c_ulong] + [_u8p] * 4 + [ctypes.c_ulong] + [_u8p] * 5
+_lib.fd_ed25519_hip_precompile_host.argtypes = [ctypes.c_void_p, ctypes.c_ulong] + [_u8p] * 5
+
+
+def precompile_work_bytes(ntxn, n_ent):
+    """FD_ED25519_HIP_PRECOMPILE_WORK_BYTES"""
+    return 111 * int(n_ent) + 3 * int(ntxn) + 16
+
+
+def precompile_count(payload):
+    """fd_ed25519_hip_precompile_count: the entries to reserve for one raw
+    transaction (host only)."""
+    payload = bytes(payload)
+    return _lib.fd_ed25519_hip_precompile_count(payload, len(payload))
+
+
+def precompile_plan(payload):
+    """fd_ed25519_hip_precompile_plan: (entries as PRECOMPILE_ENT_DTYPE
+    records, parse-or-header code, index of the first instruction whose
+    header fails or 0xFF) of one raw transaction (host only)."""
+    payload = bytes(payload)
+    ents = np.zeros(PRECOMPILE_ENT_MAX, PRECOMPILE_ENT_DTYPE)
+    code, instr = ctypes.c_byte(0), ctypes.c_ubyte(0)
+    n = _lib.fd_ed25519_hip_precompile_plan(payload, len(payload), ents.ctypes.data, len(ents), ctypes.byref(code),
+                                            ctypes.byref(instr))
+    return ents[:n], code.value, instr.value
 _lib.fd_ed25519_hip_last_error.restype = ctypes.c_char_p
 
 
@@ -227,6 +268,25 @@ class Engine:
 
     def txn_combine_dev(self, ntxn, d_sig_codes, d_first, d_cnt, d_out, stream=None):
         _check(_lib.fd_ed25519_hip_txn_combine_dev(self._h, int(ntxn), d_sig_codes, d_first, d_cnt, d_out, stream))
+
+    def precompile_host(self, payloads):
+        """The Ed25519 precompile instructions of raw transactions
+        (fd_ed25519_hip_precompile_host) -> (int8 code per transaction,
+        uint8 index of the failing instruction or 0xFF); synchronous."""
+        from .tile import pack_payloads
+        n = len(payloads)
+        codes, instr = np.zeros(n, np.int8), np.full(n, 0xFF, np.uint8)
+        if n:
+            buf, off, sz = pack_payloads(payloads)
+            _check(_lib.fd_ed25519_hip_precompile_host(self._h, n, _ptr(buf), _ptr(off), _ptr(sz), _ptr(codes),
+                                                       _ptr(instr)))
+        return codes, instr
+
+    def precompile_dev(self, ntxn, d_payloads, d_off, d_sz, d_ent_first, n_ent, d_work, d_txn_out, d_instr_out,
+                       d_ent_out=None, stream=None):
+        """Device-resident fd_ed25519_hip_precompile_dev: device addresses (ints); async."""
+        _check(_lib.fd_ed25519_hip_precompile_dev(self._h, int(ntxn), d_payloads, d_off, d_sz, d_ent_first, int(n_ent),
+                                                  d_work, d_txn_out, d_instr_out, d_ent_out, stream))
 
 
     # ---- batched signing / synthetic workloads -------------------------

@@ -209,13 +209,14 @@ typedef struct fd_ed25519_hip_engine fd_ed25519_hip_engine_t;
    vservice stats' leaked_on_hang, the drop-ins' device-lost state, the
    dsm16 form and its flag; 9: shlink protocol 6, flock-owned links; 10:
    the drop-in's and the pipe's host-scalar, host-decode and split-waves
-   setters, latency_set_cpus).  A consumer checks
+   setters, latency_set_cpus; 11: Part 2b, the Ed25519 precompile
+   instructions of raw transactions).  A consumer checks
    the library it loaded against the header it was built with:
    fd_ed25519_hip_abi_check( FD_ED25519_HIP_ABI_VERSION,
    sizeof(fd_ed25519_hip_slot_t), sizeof(fd_ed25519_hip_info_t),
    sizeof(fd_ed25519_hip_vservice_stats_t) ) returns 0 when they agree,
    FD_ED25519_HIP_ERR_INVAL (with fd_ed25519_hip_last_error) when not. */
-#define FD_ED25519_HIP_ABI_VERSION (10U)
+#define FD_ED25519_HIP_ABI_VERSION (11U)
 
 unsigned
 fd_ed25519_hip_abi_version( void );
@@ -433,6 +434,137 @@ fd_ed25519_hip_verify_txns_host( fd_ed25519_hip_engine_t * engine,
                                  unsigned char const *     pubs,
                                  signed char *             out_txn,
                                  signed char *             out_sig );
+
+/* ---- Part 2b: Ed25519 precompile instructions of raw transactions ---- */
+
+/* Besides the signatures of its signature section, a Solana transaction
+   carries the Ed25519 signatures its Ed25519SigVerify111... precompile
+   instructions name.  The reference verifies those one fd_ed25519_verify
+   call at a time (fd_precompile_ed25519_verify,
+   src/flamenco/runtime/program/fd_precompiles.c:115-200); the entry points
+   below take a batch of raw payloads and do the parse, the walk of every
+   offsets table (cross-instruction lookups and their bounds included), the
+   gather, the verification and the reference's error priority on the
+   device.
+
+   Per transaction: the payload is parsed as fd_ed25519_hip_txn_parse
+   parses it (rejected: PRECOMPILE_PARSE_FAILED).  An instruction is an
+   Ed25519 precompile instruction exactly when its program account key is
+   the Ed25519 program id; every other instruction is ignored.  Those that
+   count are judged in instruction order, each as the reference judges it
+   (header: ERR_INSTR_DATA_SIZE; then entry by entry, a failed lookup
+   ERR_DATA_OFFSET, a signature fd_ed25519_verify rejects -- whatever its
+   code, so both code flavours agree -- ERR_SIGNATURE, the first failing
+   entry ending the instruction).  The first instruction that fails gives
+   the transaction's code and, in instr_out, its index; a transaction
+   without a failure (or without such an instruction) gets 0 and 0xFF.
+
+   The three reference codes are FD_EXECUTOR_PRECOMPILE_ERR_* of
+   src/flamenco/runtime/fd_executor.h:93-95; the two others are this
+   library's. */
+#define FD_ED25519_HIP_PRECOMPILE_ERR_SIGNATURE       ( -3)
+#define FD_ED25519_HIP_PRECOMPILE_ERR_DATA_OFFSET     ( -4)
+#define FD_ED25519_HIP_PRECOMPILE_ERR_INSTR_DATA_SIZE ( -5)
+#define FD_ED25519_HIP_PRECOMPILE_PARSE_FAILED        (-16)
+/* the caller reserved another number of entries for the transaction than
+   the device's walk of it found (precompile_dev) */
+#define FD_ED25519_HIP_PRECOMPILE_BAD_RESERVATION     (-17)
+
+/* The most entries one transaction can reserve: the headers that pass
+   hold 14 bytes per entry inside a 1232-byte payload, (1232-2)/14. */
+#define FD_ED25519_HIP_PRECOMPILE_ENT_MAX (87UL)
+
+/* The entries to reserve for one payload: the sum of the entry counts of
+   its precompile instructions whose header passes (0 for a payload the
+   parser rejects), 0..FD_ED25519_HIP_PRECOMPILE_ENT_MAX.  Host only. */
+unsigned
+fd_ed25519_hip_precompile_count( unsigned char const * payload, unsigned long payload_sz );
+
+/* One entry of a payload's staging plan: offsets relative to the payload;
+   pre is 0, or ERR_DATA_OFFSET for an entry with a failed lookup (its
+   offsets and msg_sz are 0 then). */
+typedef struct {
+  unsigned char  instr;    /* index of the precompile instruction that lists the entry */
+  signed char    pre;
+  unsigned short sig_off;
+  unsigned short pub_off;
+  unsigned short msg_off;
+  unsigned short msg_sz;
+} fd_ed25519_hip_precompile_ent_t;
+
+/* The staging plan of one payload, host only (no GPU): what the device's
+   stage kernel lays out, from the same source.  Writes the first cap of
+   the payload's precompile_count entries, in instruction then entry order,
+   and returns how many it wrote.  *parse_or_header_code (optional):
+   PRECOMPILE_PARSE_FAILED, or ERR_INSTR_DATA_SIZE with the index of the
+   first instruction whose header fails in *instr (optional; the entries of
+   instructions before it are judged ahead of it), else 0 and 0xFF. */
+int
+fd_ed25519_hip_precompile_plan( unsigned char const *             payload,
+                                unsigned long                     payload_sz,
+                                fd_ed25519_hip_precompile_ent_t * ents,
+                                unsigned long                     cap,
+                                signed char *                     parse_or_header_code,
+                                unsigned char *                   instr );
+
+/* Device workspace of precompile_dev for ntxn transactions and n_ent
+   entries: per entry the gathered signature (64) and key (32), the
+   message's offset (8) and size (4), the verify code, the lookup code and
+   the instruction index; per transaction three bytes of the walk's
+   summary. */
+#define FD_ED25519_HIP_PRECOMPILE_WORK_BYTES( ntxn, n_ent ) \
+  ( 111UL*(unsigned long)(n_ent) + 3UL*(unsigned long)(ntxn) + 16UL )
+
+/* Device-resident batch: every pointer but the engine is a device pointer.
+   Transaction t is payloads[pay_off[t] .. pay_off[t] + pay_sz[t]); the
+   caller reserved the entries [ent_first[t], ent_first[t+1]) for it from
+   fd_ed25519_hip_precompile_count (ent_first[0]==0, ent_first[ntxn]==n_ent,
+   n_ent given by value: the call reads nothing back).  A transaction whose
+   reservation differs from what the device's walk of it finds gets
+   PRECOMPILE_BAD_RESERVATION; nothing is written outside its reservation
+   and no other transaction's result changes.  txn_out[t] and instr_out[t]
+   receive the code and the failing instruction's index (0xFF: none);
+   ent_out (optional) per entry 0, ERR_DATA_OFFSET or ERR_SIGNATURE on its
+   own, whatever came before it (the transaction's status for the slots of
+   a rejected payload or a bad reservation).  work: 16-byte aligned,
+   FD_ED25519_HIP_PRECOMPILE_WORK_BYTES( ntxn, n_ent ) bytes.
+
+   Messages are read in place, so the payload buffer must stay readable at
+   least 16 bytes past the end of the last payload and start 4-byte
+   aligned (the rule of fd_ed25519_hip_verify_dev's message buffer; the
+   gather reads aligned words around unaligned signatures and keys).
+
+   Asynchronous on `stream` (NULL: the engine's) like
+   fd_ed25519_hip_verify_dev, whose phases it runs over the n_ent entries
+   (chunked by the engine's max_chunk; none when n_ent is 0): it allocates
+   nothing beyond what that call may (its second lane on an engine's first
+   multi-chunk call) and does not synchronise. */
+int
+fd_ed25519_hip_precompile_dev( fd_ed25519_hip_engine_t * engine,
+                               unsigned long             ntxn,
+                               unsigned char const *     payloads,
+                               unsigned long const *     pay_off,
+                               unsigned int const *      pay_sz,
+                               unsigned int const *      ent_first,
+                               unsigned long             n_ent,
+                               void *                    work,
+                               signed char *             txn_out,
+                               unsigned char *           instr_out,
+                               signed char *             ent_out,
+                               void *                    stream );
+
+/* Host-buffer batch, synchronous: counts every payload while packing them
+   into pinned staging memory, copies, runs precompile_dev on a workspace
+   the engine owns and copies txn_out[0..ntxn) and instr_out[0..ntxn)
+   back. */
+int
+fd_ed25519_hip_precompile_host( fd_ed25519_hip_engine_t * engine,
+                                unsigned long             ntxn,
+                                unsigned char const *     payloads,
+                                unsigned long const *     pay_off,
+                                unsigned int const *      pay_sz,
+                                signed char *             txn_out,
+                                unsigned char *           instr_out );
 
 /* ---- Part 3: batched signing and the synthetic workload generator ------ */
 
