@@ -456,6 +456,36 @@ typedef struct {
 int fd_ed25519_hip_launch_precompile_stage( fd_ed25519_precompile_stage_params_t const * p, void * stream );
 int fd_ed25519_hip_launch_precompile_finish( fd_ed25519_precompile_finish_params_t const * p, void * stream );
 
+/* ---- leader signatures of Merkle shreds (fd_ed25519_shred.hip) ---- */
+
+/* stage: one lane per shred applies fd_shred_core.h's rules, derives the
+   root and fills slot i of the verify SoA -- a dummy (zero signature,
+   msg_sz 0, zero root) for a shred that is not judged */
+typedef struct {
+  uint8_t const *  shreds;     /* shred bytes, readable 16 B past each      */
+  uint64_t const * shred_off;  /* [n]                                       */
+  uint32_t const * shred_sz;   /* [n]                                       */
+  uint64_t         n;
+  uint8_t *        sigs;       /* [n][64] out, 16-B aligned                 */
+  uint8_t *        roots;      /* [n][32] out, 16-B aligned: the messages   */
+  uint64_t *       msg_off;    /* [n] out: 32 i, into roots                 */
+  uint32_t *       msg_sz;     /* [n] out: 32, or 0                         */
+  int8_t *         pre;        /* [n] out: 0, ERR_PARSE, UNSUPPORTED, ERR_HEADER */
+} fd_ed25519_shred_stage_params_t;
+
+typedef struct {
+  int8_t const *   codes;      /* [n] the verify phases' codes              */
+  int8_t const *   pre;
+  uint8_t const *  roots;
+  uint64_t         n;
+  int8_t *         out;        /* [n]                                       */
+  uint8_t *        roots_out;  /* [n][32] 16-B aligned, or NULL             */
+  int8_t *         sig_out;    /* [n] or NULL                               */
+} fd_ed25519_shred_finish_params_t;
+
+int fd_ed25519_hip_launch_shred_stage( fd_ed25519_shred_stage_params_t const * p, void * stream );
+int fd_ed25519_hip_launch_shred_finish( fd_ed25519_shred_finish_params_t const * p, void * stream );
+
 /* ---- generator (fd_ed25519_gen.hip) ---- */
 
 typedef struct {

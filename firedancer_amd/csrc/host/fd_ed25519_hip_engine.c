@@ -23,6 +23,7 @@
 #include "../fd_ed25519_hip_internal.h"
 #include "../fd_txn_parse_core.h"
 #include "../fd_precompile_core.h"
+#include "../fd_shred_core.h"
 
 #include <hip/hip_runtime_api.h>
 #include <pthread.h>
@@ -103,6 +104,12 @@ struct fd_ed25519_hip_engine {
   uint8_t *    h_pc_in;  uint8_t *  d_pc_in;
   uint8_t *    h_pc_out; uint8_t *  d_pc_out;
   uint8_t *    d_pc_work;
+  /* shreds_host: a chunk's inputs (leaders, shred_off, shred_sz) and outputs
+     (roots, out) in one block each, and the device workspace of shreds_dev */
+  uint64_t     sh_in_cap, sh_out_cap, sh_work_cap;   /* bytes */
+  uint8_t *    h_sh_in;  uint8_t *  d_sh_in;
+  uint8_t *    h_sh_out; uint8_t *  d_sh_out;
+  uint8_t *    d_sh_work;
 
   /* per-phase event timing (bench / profiling) */
   int          timing;
@@ -392,6 +399,8 @@ engine_free( fd_ed25519_hip_engine_t * e ) {
   hipHostFree( e->h_tout );
   hipFree( e->d_pc_in ); hipFree( e->d_pc_out ); hipFree( e->d_pc_work );
   hipHostFree( e->h_pc_in ); hipHostFree( e->h_pc_out );
+  hipFree( e->d_sh_in ); hipFree( e->d_sh_out ); hipFree( e->d_sh_work );
+  hipHostFree( e->h_sh_in ); hipHostFree( e->h_sh_out );
   if( e->tm_ev_init )
     for( int i=0; i<FD_ED25519_HIP_TIMING_MAX; i++ )
       for( int j=0; j<=FD_ED25519_PHASE_CNT; j++ ) hipEventDestroy( e->tm_ev[i][j] );
@@ -1485,6 +1494,110 @@ fd_ed25519_hip_precompile_host( fd_ed25519_hip_engine_t * e, unsigned long ntxn,
   HIPCHK( hipStreamSynchronize( st ), "precompile" );
   memcpy( txn_out,   e->h_pc_out,        ntxn );
   memcpy( instr_out, e->h_pc_out + ntxn, ntxn );
+  return FD_ED25519_HIP_OK;
+}
+
+/* ---- leader signatures of Merkle shreds (include/fd_ed25519_hip.h Part 2c) -- */
+
+_Static_assert( FD_ED25519_HIP_SHRED_OK==FD_SHRED_CORE_OK && FD_ED25519_HIP_SHRED_ERR_PARSE==FD_SHRED_CORE_ERR_PARSE &&
+                FD_ED25519_HIP_SHRED_UNSUPPORTED==FD_SHRED_CORE_UNSUPPORTED &&
+                FD_ED25519_HIP_SHRED_ERR_HEADER==FD_SHRED_CORE_ERR_HEADER &&
+                FD_ED25519_HIP_SHRED_ERR_SIGNATURE==FD_SHRED_CORE_ERR_SIGNATURE,
+                "public and core shred codes differ" );
+
+/* the rules and the hashes the stage kernel runs, on the host (no GPU) */
+int
+fd_ed25519_hip_shred_root( unsigned char const * shred, unsigned long sz, unsigned char * root ) {
+  return fd_shred_core_root( shred, sz, root );
+}
+
+int
+fd_ed25519_hip_shreds_dev( fd_ed25519_hip_engine_t * e, unsigned long n, unsigned char const * shreds,
+                           unsigned long const * shred_off, unsigned int const * shred_sz,
+                           unsigned char const * leaders, void * work, signed char * out, unsigned char * roots,
+                           signed char * sig_out, void * stream ) {
+  if( !e ) return FD_ED25519_HIP_ERR_INVAL;
+  if( !n ) return FD_ED25519_HIP_OK;
+  if( !shreds || !shred_off || !shred_sz || !leaders || !work || !out ) return FD_ED25519_HIP_ERR_INVAL;
+  if( ( (uintptr_t)work | (uintptr_t)leaders | (uintptr_t)roots | (uintptr_t)shreds ) & 15UL ) {
+    snprintf( fd_ed25519_hip_errbuf, sizeof(fd_ed25519_hip_errbuf), "shreds/leaders/work/roots must be 16-byte aligned" );
+    return FD_ED25519_HIP_ERR_INVAL;
+  }
+  hipStream_t st = stream ? (hipStream_t)stream : e->stream;
+  HIPCHK( hipSetDevice( e->device ), "hipSetDevice" );
+  /* FD_ED25519_HIP_SHRED_WORK_BYTES: [n] sigs 64, roots 32, msg_off 8, msg_sz
+     4, codes, pre 1 each (every array aligned to its element at any n; the
+     roots, being the verify messages, have the arrays behind them and the
+     16 spare bytes to be read past) */
+  uint8_t * w = (uint8_t *)work;
+  fd_ed25519_shred_stage_params_t sp;
+  memset( &sp, 0, sizeof(sp) );
+  sp.shreds = shreds; sp.shred_off = (uint64_t const *)shred_off; sp.shred_sz = shred_sz; sp.n = n;
+  sp.sigs    = w;
+  sp.roots   = w +  64UL*n;
+  sp.msg_off = (uint64_t *)( w +  96UL*n );
+  sp.msg_sz  = (uint32_t *)( w + 104UL*n );
+  int8_t * codes = (int8_t *)( w + 108UL*n );
+  sp.pre     = (int8_t *)( w + 109UL*n );
+  int err = fd_ed25519_hip_launch_shred_stage( &sp, st );
+  if( err ) return hip_fail( (hipError_t)err, "shred_stage launch" );
+  err = verify_common( e, n, sp.roots, (unsigned long const *)sp.msg_off, sp.msg_sz, NULL, sp.sigs, leaders,
+                       (signed char *)codes, st );
+  if( err ) return err;
+  fd_ed25519_shred_finish_params_t fp;
+  memset( &fp, 0, sizeof(fp) );
+  fp.codes = codes; fp.pre = sp.pre; fp.roots = sp.roots; fp.n = n;
+  fp.out = (int8_t *)out; fp.roots_out = roots; fp.sig_out = (int8_t *)sig_out;
+  err = fd_ed25519_hip_launch_shred_finish( &fp, st );
+  if( err ) return hip_fail( (hipError_t)err, "shred_finish launch" );
+  return FD_ED25519_HIP_OK;
+}
+
+/* shreds per pass of shreds_host: bounds the pinned staging (20 MiB of
+   shred bytes) whatever n is */
+#define SHREDS_HOST_CHUNK 16384UL
+
+int
+fd_ed25519_hip_shreds_host( fd_ed25519_hip_engine_t * e, unsigned long n, unsigned char const * shreds,
+                            unsigned long const * shred_off, unsigned int const * shred_sz,
+                            unsigned char const * leaders, signed char * out, unsigned char * roots ) {
+  if( !e ) return FD_ED25519_HIP_ERR_INVAL;
+  if( !n ) return FD_ED25519_HIP_OK;
+  if( !shreds || !shred_off || !shred_sz || !leaders || !out ) return FD_ED25519_HIP_ERR_INVAL;
+  HIPCHK( hipSetDevice( e->device ), "hipSetDevice" );
+  hipStream_t st = e->stream;
+  int err;
+  for( uint64_t base=0UL; base<n; base+=SHREDS_HOST_CHUNK ) {
+    uint64_t m = n-base<SHREDS_HOST_CHUNK ? n-base : SHREDS_HOST_CHUNK;
+    /* in: leaders 32 [m], shred_off u64 [m], shred_sz u32 [m]; out: roots 32 [m], out [m] */
+    if( (err = stage_msgs( e, m*FD_SHRED_CORE_MAX_SZ )) ) return err;   /* 64 bytes of room behind the last shred */
+    if( (err = grow_pair( (void **)&e->h_sh_in,  (void **)&e->d_sh_in,  &e->sh_in_cap,  44UL*m, 1UL )) ) return err;
+    if( (err = grow_pair( (void **)&e->h_sh_out, (void **)&e->d_sh_out, &e->sh_out_cap, 33UL*m, 1UL )) ) return err;
+    if( (err = grow_dev( &e->d_sh_work, &e->sh_work_cap, FD_ED25519_HIP_SHRED_WORK_BYTES( m ) )) ) return err;
+    uint64_t * h_off = (uint64_t *)( e->h_sh_in + 32UL*m );
+    uint32_t * h_sz  = (uint32_t *)( e->h_sh_in + 40UL*m );
+    memcpy( e->h_sh_in, leaders + 32UL*base, 32UL*m );
+    uint64_t pos = 0UL;
+    for( uint64_t i=0UL; i<m; i++ ) {
+      /* no rule reads a byte at or past FD_SHRED_MAX_SZ, so a longer shred
+         travels as its head and its true size */
+      uint64_t sz = shred_sz[base+i], cp = sz<FD_SHRED_CORE_MAX_SZ ? sz : FD_SHRED_CORE_MAX_SZ;
+      if( cp ) memcpy( e->h_msgs + pos, shreds + shred_off[base+i], cp );
+      h_off[i] = pos;
+      h_sz [i] = (uint32_t)sz;
+      pos += cp;
+    }
+    HIPCHK( hipMemcpyAsync( e->d_msgs, e->h_msgs, pos ? pos : 1UL, hipMemcpyHostToDevice, st ), "H2D shreds" );
+    HIPCHK( hipMemcpyAsync( e->d_sh_in, e->h_sh_in, 44UL*m, hipMemcpyHostToDevice, st ), "H2D shreds in" );
+    if( (err = fd_ed25519_hip_shreds_dev( e, m, e->d_msgs, (unsigned long const *)( e->d_sh_in + 32UL*m ),
+                                          (unsigned int const *)( e->d_sh_in + 40UL*m ), e->d_sh_in, e->d_sh_work,
+                                          (signed char *)( e->d_sh_out + 32UL*m ), roots ? e->d_sh_out : NULL, NULL,
+                                          st )) ) return err;
+    HIPCHK( hipMemcpyAsync( e->h_sh_out, e->d_sh_out, 33UL*m, hipMemcpyDeviceToHost, st ), "D2H shreds out" );
+    HIPCHK( hipStreamSynchronize( st ), "shreds" );
+    memcpy( out + base, e->h_sh_out + 32UL*m, m );
+    if( roots ) memcpy( roots + 32UL*base, e->h_sh_out, 32UL*m );
+  }
   return FD_ED25519_HIP_OK;
 }
 

@@ -132,6 +132,31 @@ def precompile_plan(payload):
     n = _lib.fd_ed25519_hip_precompile_plan(payload, len(payload), ents.ctypes.data, len(ents), ctypes.byref(code),
                                             ctypes.byref(instr))
     return ents[:n], code.value, instr.value
+
+
+# leader signatures of Merkle shreds (include/fd_ed25519_hip.h Part 2c)
+SHRED_OK = 0
+SHRED_ERR_PARSE = -16
+SHRED_UNSUPPORTED = -18
+SHRED_ERR_HEADER = -19
+SHRED_ERR_SIGNATURE = -20
+_lib.fd_ed25519_hip_shred_root.argtypes = [ctypes.c_char_p, ctypes.c_ulong, ctypes.c_char_p]
+_lib.fd_ed25519_hip_shreds_dev.argtypes = [ctypes.c_void_p, ctypes.c_ulong] + [_u8p] * 9
+_lib.fd_ed25519_hip_shreds_host.argtypes = [ctypes.c_void_p, ctypes.c_ulong] + [_u8p] * 6
+
+
+def shred_work_bytes(n):
+    """FD_ED25519_HIP_SHRED_WORK_BYTES"""
+    return 110 * int(n) + 16
+
+
+def shred_root(shred):
+    """fd_ed25519_hip_shred_root: (code, the 32-byte Merkle root the leader
+    signed or None) of one raw shred (host only)."""
+    shred = bytes(shred)
+    root = ctypes.create_string_buffer(32)
+    code = _lib.fd_ed25519_hip_shred_root(shred, len(shred), root)
+    return code, (root.raw if code == 0 else None)
 _lib.fd_ed25519_hip_last_error.restype = ctypes.c_char_p
 
 
@@ -281,6 +306,29 @@ class Engine:
             _check(_lib.fd_ed25519_hip_precompile_host(self._h, n, _ptr(buf), _ptr(off), _ptr(sz), _ptr(codes),
                                                        _ptr(instr)))
         return codes, instr
+
+    def shreds_host(self, shreds, leaders):
+        """The leader signatures of raw Merkle shreds
+        (fd_ed25519_hip_shreds_host): leaders is one 32-byte key per shred,
+        or one key for all -> (int8 code per shred, uint8 [n, 32] derived
+        roots, zero where none was derived); synchronous."""
+        from .tile import pack_payloads
+        n = len(shreds)
+        codes, roots = np.zeros(n, np.int8), np.zeros((n, 32), np.uint8)
+        if n:
+            if isinstance(leaders, (bytes, bytearray)):
+                leaders = [bytes(leaders)] * n
+            keys = np.frombuffer(b"".join(bytes(k) for k in leaders), np.uint8)
+            assert keys.size == 32 * n
+            buf, off, sz = pack_payloads(shreds)
+            _check(_lib.fd_ed25519_hip_shreds_host(self._h, n, _ptr(buf), _ptr(off), _ptr(sz), _ptr(keys), _ptr(codes),
+                                                   _ptr(roots)))
+        return codes, roots
+
+    def shreds_dev(self, n, d_shreds, d_off, d_sz, d_leaders, d_work, d_out, d_roots=None, d_sig_out=None, stream=None):
+        """Device-resident fd_ed25519_hip_shreds_dev: device addresses (ints); async."""
+        _check(_lib.fd_ed25519_hip_shreds_dev(self._h, int(n), d_shreds, d_off, d_sz, d_leaders, d_work, d_out, d_roots,
+                                              d_sig_out, stream))
 
     def precompile_dev(self, ntxn, d_payloads, d_off, d_sz, d_ent_first, n_ent, d_work, d_txn_out, d_instr_out,
                        d_ent_out=None, stream=None):

@@ -210,13 +210,14 @@ typedef struct fd_ed25519_hip_engine fd_ed25519_hip_engine_t;
    dsm16 form and its flag; 9: shlink protocol 6, flock-owned links; 10:
    the drop-in's and the pipe's host-scalar, host-decode and split-waves
    setters, latency_set_cpus; 11: Part 2b, the Ed25519 precompile
-   instructions of raw transactions).  A consumer checks
+   instructions of raw transactions; 12: Part 2c, the leader signatures of
+   Merkle shreds).  A consumer checks
    the library it loaded against the header it was built with:
    fd_ed25519_hip_abi_check( FD_ED25519_HIP_ABI_VERSION,
    sizeof(fd_ed25519_hip_slot_t), sizeof(fd_ed25519_hip_info_t),
    sizeof(fd_ed25519_hip_vservice_stats_t) ) returns 0 when they agree,
    FD_ED25519_HIP_ERR_INVAL (with fd_ed25519_hip_last_error) when not. */
-#define FD_ED25519_HIP_ABI_VERSION (11U)
+#define FD_ED25519_HIP_ABI_VERSION (12U)
 
 unsigned
 fd_ed25519_hip_abi_version( void );
@@ -565,6 +566,100 @@ fd_ed25519_hip_precompile_host( fd_ed25519_hip_engine_t * engine,
                                 unsigned int const *      pay_sz,
                                 signed char *             txn_out,
                                 unsigned char *           instr_out );
+
+/* ---- Part 2c: the leader signatures of Merkle shreds -------------------- */
+
+/* A validator checks every incoming Merkle shred that opens a FEC set
+   against its slot leader's key before it reserves anything for the set
+   (fd_fec_resolver_add_shred, src/disco/shred/fd_fec_resolver.c:283-440):
+   it parses the shred (fd_shred_parse, src/ballet/shred/fd_shred.c:3-72),
+   rejects impossible headers (:311-359), hashes about a kilobyte of the
+   shred into a Merkle leaf, walks the shred's inclusion proof of 20-byte
+   nodes up to the 32-byte root and calls fd_ed25519_verify( root, 32,
+   shred->signature, leader_pubkey ).  The entry points below take a batch of
+   raw shreds with their leaders' keys and do all of that on the device.
+
+   Per shred: a shred fd_shred_parse rejects gets SHRED_ERR_PARSE.  The
+   resolver of this reference handles unchained Merkle shreds only (variant
+   0x8? data, 0x4? code); every other variant that parses (chained, resigned,
+   legacy) gets SHRED_UNSUPPORTED and belongs on the caller's CPU path.  A
+   judged shred with an all-zero signature, a code shred with data_cnt or
+   code_cnt zero or above 67, an index inside its FEC set of 67 or more, or
+   a proof too short for its index gets SHRED_ERR_HEADER; one whose derived
+   root fd_ed25519_verify does not accept under the leader's key -- whatever
+   its code, so both code flavours agree -- gets SHRED_ERR_SIGNATURE; every
+   other shred gets 0.  SHRED_ERR_HEADER and SHRED_ERR_SIGNATURE are where
+   the resolver returns FD_FEC_RESOLVER_SHRED_REJECTED for a shred that
+   opens a set.  The resolver's state (its map of sets, duplicates,
+   consistency with a set's earlier shreds, Reed-Solomon recovery) stays
+   with the caller.  All five codes are this library's. */
+#define FD_ED25519_HIP_SHRED_OK            (  0)
+#define FD_ED25519_HIP_SHRED_ERR_PARSE     (-16)
+#define FD_ED25519_HIP_SHRED_UNSUPPORTED   (-18)
+#define FD_ED25519_HIP_SHRED_ERR_HEADER    (-19)
+#define FD_ED25519_HIP_SHRED_ERR_SIGNATURE (-20)
+
+/* The root one shred's leader signed, host only (no GPU), from the same
+   source as the device's stage kernel: parses, applies the header rules,
+   hashes the leaf and walks the proof.  Returns 0 with root[0..32) written,
+   else SHRED_ERR_PARSE, SHRED_UNSUPPORTED or SHRED_ERR_HEADER (root
+   untouched).  Reads shred[0..sz) only. */
+int
+fd_ed25519_hip_shred_root( unsigned char const * shred,
+                           unsigned long         sz,
+                           unsigned char *       root );
+
+/* Device workspace of shreds_dev for n shreds: per shred the root as the
+   verify message (32), the gathered signature (64), the message's offset
+   (8) and size (4), the verify code and the stage's code. */
+#define FD_ED25519_HIP_SHRED_WORK_BYTES( n ) ( 110UL*(unsigned long)(n) + 16UL )
+
+/* Device-resident batch: every pointer but the engine is a device pointer.
+   Shred i is shreds[shred_off[i] .. shred_off[i] + shred_sz[i]) and may
+   start at any byte; leaders + 32 i is its slot leader's public key (the
+   array 16-byte aligned: the verify phases read it in place).  out[i]
+   receives the shred's code.  roots (optional, 16-byte aligned) receives
+   the derived root of every judged shred that passed the header rules at
+   roots + 32 i, 32 zero bytes for any other; sig_out (optional) fd_ed25519_verify's own code for
+   the same shreds (in the engine's code flavour) and 0 for any other.
+   work: 16-byte aligned, FD_ED25519_HIP_SHRED_WORK_BYTES( n ) bytes.
+
+   The shred buffer must start 16-byte aligned and stay readable at least
+   16 bytes past the end of the last shred (the rule of
+   fd_ed25519_hip_verify_dev's message buffer: the stage reads aligned
+   words around unaligned bytes).
+
+   Asynchronous on `stream` (NULL: the engine's) like
+   fd_ed25519_hip_verify_dev, whose phases it runs over the n roots
+   (chunked by the engine's max_chunk): it allocates nothing beyond what
+   that call may (its second lane on an engine's first multi-chunk call)
+   and does not synchronise. */
+int
+fd_ed25519_hip_shreds_dev( fd_ed25519_hip_engine_t * engine,
+                           unsigned long             n,
+                           unsigned char const *     shreds,
+                           unsigned long const *     shred_off,
+                           unsigned int const *      shred_sz,
+                           unsigned char const *     leaders,
+                           void *                    work,
+                           signed char *             out,
+                           unsigned char *           roots,
+                           signed char *             sig_out,
+                           void *                    stream );
+
+/* Host-buffer batch, synchronous: packs the shreds into pinned staging
+   memory (in chunks, so any n fits), copies, runs shreds_dev on a
+   workspace the engine owns and copies out[0..n) and, when roots is not
+   NULL, roots[0..32 n) back. */
+int
+fd_ed25519_hip_shreds_host( fd_ed25519_hip_engine_t * engine,
+                            unsigned long             n,
+                            unsigned char const *     shreds,
+                            unsigned long const *     shred_off,
+                            unsigned int const *      shred_sz,
+                            unsigned char const *     leaders,
+                            signed char *             out,
+                            unsigned char *           roots );
 
 /* ---- Part 3: batched signing and the synthetic workload generator ------ */
 

@@ -1,0 +1,42 @@
+"""Hostile input to the shred rules and hashes: fd_shred_core.h compiled with a
+stand-alone main (tests/shred_walk_main.c) under ASan and UBSan, run on
+mutated, rule-edge and truncated shreds held in heap blocks of exactly their
+size.  A program of its own: nothing is loaded into this interpreter."""
+import os
+import struct
+import subprocess
+
+import pytest
+
+from conftest import REPO
+from shred_util import every_depth, fixture, mutated, rule_cases
+
+
+@pytest.fixture(scope="module")
+def walker(tmp_path_factory):
+    exe = tmp_path_factory.mktemp("shred_walk") / "shred_walk"
+    r = subprocess.run(["gcc", "-std=c11", "-O1", "-g", "-Wall", "-Wextra", "-Werror", "-fsanitize=address,undefined",
+                        "-fno-sanitize-recover=all", "-fno-omit-frame-pointer", "-static-libasan", "-static-libubsan",
+                        "-I" + os.path.join(REPO, "firedancer_amd", "csrc"),
+                        os.path.join(REPO, "tests", "shred_walk_main.c"), "-o", str(exe)],
+                       capture_output=True, text=True)
+    assert r.returncode == 0, r.stderr
+    return str(exe)
+
+
+def test_walk_of_hostile_shreds_is_clean_and_agrees_with_the_library(walker, oracle, tmp_path):
+    from firedancer_amd import ed25519 as ed
+    shreds = list(mutated()) + [s for _, s, _ in rule_cases(oracle)[0]] + every_depth(oracle)[0]
+    # and every prefix of one captured data shred and of one code shred's header
+    data = next(s for s in fixture()[0] if len(s) == 1203)
+    code = next(s for s in fixture()[0] if len(s) == 1228)
+    shreds += [data[:k] for k in range(len(data))] + [code[:k] for k in range(0x50, 0x60)] + [code[:1227]]
+    path = tmp_path / "shreds.bin"
+    path.write_bytes(struct.pack("<I", len(shreds)) + b"".join(struct.pack("<I", len(s)) + s for s in shreds))
+    r = subprocess.run([walker, str(path)], capture_output=True, text=True, timeout=120)
+    assert r.returncode == 0, (r.returncode, r.stderr[-3000:])
+    lines = r.stdout.split("\n")[:-1]
+    assert len(lines) == len(shreds)
+    for s, line in zip(shreds, lines):
+        c, root = ed.shred_root(s)
+        assert line.split() == [str(c), root.hex() if root else "-"], (s[:0x60].hex(), line)
