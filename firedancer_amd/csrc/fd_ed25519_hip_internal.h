@@ -486,6 +486,39 @@ typedef struct {
 int fd_ed25519_hip_launch_shred_stage( fd_ed25519_shred_stage_params_t const * p, void * stream );
 int fd_ed25519_hip_launch_shred_finish( fd_ed25519_shred_finish_params_t const * p, void * stream );
 
+/* ---- signed gossip and repair control packets (fd_ed25519_packet.hip) ---- */
+
+/* stage: one lane per packet applies fd_packet_core.h's rules and fills slot
+   i of the verify SoA -- signature, key, and the message in the mirror of
+   the packet buffer; a dummy (zero signature and key, msg_sz 0) for a packet
+   that is not judged */
+typedef struct {
+  uint8_t const *  pkts;       /* 16-B aligned, readable 16 B past pkt_bytes */
+  uint64_t const * pkt_off;    /* [n]                                        */
+  uint32_t const * pkt_sz;     /* [n]                                        */
+  uint64_t         n;
+  uint64_t         pkt_bytes;
+  uint32_t         self_key[ 8 ];  /* the own identity, by value             */
+  int32_t          proto;
+  uint8_t *        sigs;       /* [n][64] out, 16-B aligned                  */
+  uint8_t *        pubs;       /* [n][32] out, 16-B aligned                  */
+  uint8_t *        msgs;       /* mirror of pkts out, 16-B aligned           */
+  uint64_t *       msg_off;    /* [n] out, into msgs                         */
+  uint32_t *       msg_sz;     /* [n] out                                    */
+  int8_t *         pre;        /* [n] out: 0, ERR_PARSE, UNSUPPORTED, NOT_FOR_SELF */
+} fd_ed25519_packet_stage_params_t;
+
+typedef struct {
+  int8_t const *   codes;      /* [n] the verify phases' codes               */
+  int8_t const *   pre;
+  uint64_t         n;
+  int8_t *         out;        /* [n]                                        */
+  int8_t *         sig_out;    /* [n] or NULL                                */
+} fd_ed25519_packet_finish_params_t;
+
+int fd_ed25519_hip_launch_packet_stage( fd_ed25519_packet_stage_params_t const * p, void * stream );
+int fd_ed25519_hip_launch_packet_finish( fd_ed25519_packet_finish_params_t const * p, void * stream );
+
 /* ---- generator (fd_ed25519_gen.hip) ---- */
 
 typedef struct {

@@ -24,6 +24,7 @@
 #include "../fd_txn_parse_core.h"
 #include "../fd_precompile_core.h"
 #include "../fd_shred_core.h"
+#include "../fd_packet_core.h"
 
 #include <hip/hip_runtime_api.h>
 #include <pthread.h>
@@ -110,6 +111,11 @@ struct fd_ed25519_hip_engine {
   uint8_t *    h_sh_in;  uint8_t *  d_sh_in;
   uint8_t *    h_sh_out; uint8_t *  d_sh_out;
   uint8_t *    d_sh_work;
+  /* packets_host: a pass's inputs (pkt_off, pkt_sz) and the device workspace
+     of packets_dev; the codes come back through h_sh_out / d_sh_out */
+  uint64_t     pk_in_cap, pk_work_cap;               /* bytes */
+  uint8_t *    h_pk_in;  uint8_t *  d_pk_in;
+  uint8_t *    d_pk_work;
 
   /* per-phase event timing (bench / profiling) */
   int          timing;
@@ -401,6 +407,7 @@ engine_free( fd_ed25519_hip_engine_t * e ) {
   hipHostFree( e->h_pc_in ); hipHostFree( e->h_pc_out );
   hipFree( e->d_sh_in ); hipFree( e->d_sh_out ); hipFree( e->d_sh_work );
   hipHostFree( e->h_sh_in ); hipHostFree( e->h_sh_out );
+  hipFree( e->d_pk_in ); hipFree( e->d_pk_work ); hipHostFree( e->h_pk_in );
   if( e->tm_ev_init )
     for( int i=0; i<FD_ED25519_HIP_TIMING_MAX; i++ )
       for( int j=0; j<=FD_ED25519_PHASE_CNT; j++ ) hipEventDestroy( e->tm_ev[i][j] );
@@ -1597,6 +1604,124 @@ fd_ed25519_hip_shreds_host( fd_ed25519_hip_engine_t * e, unsigned long n, unsign
     HIPCHK( hipStreamSynchronize( st ), "shreds" );
     memcpy( out + base, e->h_sh_out + 32UL*m, m );
     if( roots ) memcpy( roots + 32UL*base, e->h_sh_out, 32UL*m );
+  }
+  return FD_ED25519_HIP_OK;
+}
+
+/* ---- signed gossip and repair control packets (include/fd_ed25519_hip.h Part 2d) -- */
+
+_Static_assert( FD_ED25519_HIP_PACKET_OK==FD_PACKET_CORE_OK && FD_ED25519_HIP_PACKET_ERR_PARSE==FD_PACKET_CORE_ERR_PARSE &&
+                FD_ED25519_HIP_PACKET_UNSUPPORTED==FD_PACKET_CORE_UNSUPPORTED &&
+                FD_ED25519_HIP_PACKET_ERR_SIGNATURE==FD_PACKET_CORE_ERR_SIGNATURE &&
+                FD_ED25519_HIP_PACKET_NOT_FOR_SELF==FD_PACKET_CORE_NOT_FOR_SELF &&
+                FD_ED25519_HIP_PROTO_GOSSIP==FD_PACKET_CORE_PROTO_GOSSIP &&
+                FD_ED25519_HIP_PROTO_REPAIR_SERV==FD_PACKET_CORE_PROTO_REPAIR_SERV &&
+                FD_ED25519_HIP_PACKET_MAX==FD_PACKET_CORE_MAX &&
+                sizeof(fd_ed25519_hip_packet_plan_t)==sizeof(fd_packet_core_plan_t),
+                "public and core packet constants differ" );
+
+static int
+packet_proto_ok( int proto ) {
+  return ( proto==FD_ED25519_HIP_PROTO_GOSSIP ) | ( proto==FD_ED25519_HIP_PROTO_REPAIR_SERV );
+}
+
+/* the rules the stage kernel runs, on the host (no GPU) */
+int
+fd_ed25519_hip_packet_plan( int proto, unsigned char const * pkt, unsigned long sz, unsigned char const self_key[ 32 ],
+                            fd_ed25519_hip_packet_plan_t * plan ) {
+  if( !packet_proto_ok( proto ) || !self_key || !plan ) return FD_ED25519_HIP_ERR_INVAL;
+  fd_packet_core_plan_t c;
+  int code = fd_packet_core_plan( proto, pkt, sz, self_key, &c );
+  memcpy( plan, &c, sizeof(c) );
+  return code;
+}
+
+int
+fd_ed25519_hip_packets_dev( fd_ed25519_hip_engine_t * e, int proto, unsigned long n, unsigned char const * pkts,
+                            unsigned long const * pkt_off, unsigned int const * pkt_sz, unsigned long pkt_bytes,
+                            unsigned char const self_key[ 32 ], void * work, signed char * out, signed char * sig_out,
+                            void * stream ) {
+  if( !e || !packet_proto_ok( proto ) || !self_key ) return FD_ED25519_HIP_ERR_INVAL;
+  if( !n ) return FD_ED25519_HIP_OK;
+  if( !pkts || !pkt_off || !pkt_sz || !work || !out ) return FD_ED25519_HIP_ERR_INVAL;
+  if( ( (uintptr_t)work | (uintptr_t)pkts ) & 15UL ) {
+    snprintf( fd_ed25519_hip_errbuf, sizeof(fd_ed25519_hip_errbuf), "pkts/work must be 16-byte aligned" );
+    return FD_ED25519_HIP_ERR_INVAL;
+  }
+  hipStream_t st = stream ? (hipStream_t)stream : e->stream;
+  HIPCHK( hipSetDevice( e->device ), "hipSetDevice" );
+  /* FD_ED25519_HIP_PACKET_WORK_BYTES: [n] sigs 64, pubs 32, then the mirror
+     of the packet buffer (pkt_bytes + 16 rounded up to 16: the messages,
+     with the 16 spare bytes to be read past), then [n] msg_off 8, msg_sz 4,
+     codes, pre 1 each (every array aligned to its element at any n) */
+  uint8_t * w = (uint8_t *)work;
+  uint64_t  mirror = ( (uint64_t)pkt_bytes + 31UL ) & ~15UL;
+  fd_ed25519_packet_stage_params_t sp;
+  memset( &sp, 0, sizeof(sp) );
+  sp.pkts = pkts; sp.pkt_off = (uint64_t const *)pkt_off; sp.pkt_sz = pkt_sz; sp.n = n; sp.pkt_bytes = pkt_bytes;
+  memcpy( sp.self_key, self_key, 32UL );
+  sp.proto   = proto;
+  sp.sigs    = w;
+  sp.pubs    = w +  64UL*n;
+  sp.msgs    = w +  96UL*n;
+  sp.msg_off = (uint64_t *)( w +  96UL*n + mirror );
+  sp.msg_sz  = (uint32_t *)( w + 104UL*n + mirror );
+  int8_t * codes = (int8_t *)( w + 108UL*n + mirror );
+  sp.pre     = (int8_t *)( w + 109UL*n + mirror );
+  int err = fd_ed25519_hip_launch_packet_stage( &sp, st );
+  if( err ) return hip_fail( (hipError_t)err, "packet_stage launch" );
+  err = verify_common( e, n, sp.msgs, (unsigned long const *)sp.msg_off, sp.msg_sz, NULL, sp.sigs, sp.pubs,
+                       (signed char *)codes, st );
+  if( err ) return err;
+  fd_ed25519_packet_finish_params_t fp;
+  memset( &fp, 0, sizeof(fp) );
+  fp.codes = codes; fp.pre = sp.pre; fp.n = n; fp.out = (int8_t *)out; fp.sig_out = (int8_t *)sig_out;
+  err = fd_ed25519_hip_launch_packet_finish( &fp, st );
+  if( err ) return hip_fail( (hipError_t)err, "packet_finish launch" );
+  return FD_ED25519_HIP_OK;
+}
+
+/* packets per pass of packets_host: bounds the pinned staging (20 MiB of
+   packet bytes) whatever n is */
+#define PACKETS_HOST_CHUNK 16384UL
+
+int
+fd_ed25519_hip_packets_host( fd_ed25519_hip_engine_t * e, int proto, unsigned long n, unsigned char const * pkts,
+                             unsigned long const * pkt_off, unsigned int const * pkt_sz,
+                             unsigned char const self_key[ 32 ], signed char * out ) {
+  if( !e || !packet_proto_ok( proto ) || !self_key ) return FD_ED25519_HIP_ERR_INVAL;
+  if( !n ) return FD_ED25519_HIP_OK;
+  if( !pkts || !pkt_off || !pkt_sz || !out ) return FD_ED25519_HIP_ERR_INVAL;
+  HIPCHK( hipSetDevice( e->device ), "hipSetDevice" );
+  hipStream_t st = e->stream;
+  int err;
+  for( uint64_t base=0UL; base<n; base+=PACKETS_HOST_CHUNK ) {
+    uint64_t m = n-base<PACKETS_HOST_CHUNK ? n-base : PACKETS_HOST_CHUNK;
+    /* in: pkt_off u64 [m], pkt_sz u32 [m]; out: out [m] */
+    if( (err = stage_msgs( e, m*FD_PACKET_CORE_MAX )) ) return err;   /* 64 bytes of room behind the last packet */
+    if( (err = grow_pair( (void **)&e->h_pk_in,  (void **)&e->d_pk_in,  &e->pk_in_cap,  12UL*m, 1UL )) ) return err;
+    if( (err = grow_pair( (void **)&e->h_sh_out, (void **)&e->d_sh_out, &e->sh_out_cap, m,      1UL )) ) return err;
+    uint64_t * h_off = (uint64_t *)e->h_pk_in;
+    uint32_t * h_sz  = (uint32_t *)( e->h_pk_in + 8UL*m );
+    uint64_t pos = 0UL;
+    for( uint64_t i=0UL; i<m; i++ ) {
+      /* no rule reads a packet of more than FD_ED25519_HIP_PACKET_MAX bytes:
+         it travels as its true size alone, and leaves the packed range */
+      uint64_t sz = pkt_sz[base+i], cp = sz<=FD_PACKET_CORE_MAX ? sz : 0UL;
+      if( cp ) memcpy( e->h_msgs + pos, pkts + pkt_off[base+i], cp );
+      h_off[i] = pos;
+      h_sz [i] = (uint32_t)sz;
+      pos += cp;
+    }
+    if( (err = grow_dev( &e->d_pk_work, &e->pk_work_cap, FD_ED25519_HIP_PACKET_WORK_BYTES( m, pos ) )) ) return err;
+    HIPCHK( hipMemcpyAsync( e->d_msgs, e->h_msgs, pos ? pos : 1UL, hipMemcpyHostToDevice, st ), "H2D packets" );
+    HIPCHK( hipMemcpyAsync( e->d_pk_in, e->h_pk_in, 12UL*m, hipMemcpyHostToDevice, st ), "H2D packets in" );
+    if( (err = fd_ed25519_hip_packets_dev( e, proto, m, e->d_msgs, (unsigned long const *)e->d_pk_in,
+                                           (unsigned int const *)( e->d_pk_in + 8UL*m ), pos, self_key, e->d_pk_work,
+                                           (signed char *)e->d_sh_out, NULL, st )) ) return err;
+    HIPCHK( hipMemcpyAsync( e->h_sh_out, e->d_sh_out, m, hipMemcpyDeviceToHost, st ), "D2H packets out" );
+    HIPCHK( hipStreamSynchronize( st ), "packets" );
+    memcpy( out + base, e->h_sh_out, m );
   }
   return FD_ED25519_HIP_OK;
 }

@@ -157,6 +157,49 @@ def shred_root(shred):
     root = ctypes.create_string_buffer(32)
     code = _lib.fd_ed25519_hip_shred_root(shred, len(shred), root)
     return code, (root.raw if code == 0 else None)
+
+
+# signed gossip and repair control packets (include/fd_ed25519_hip.h Part 2d)
+PROTO_GOSSIP = 0
+PROTO_REPAIR_SERV = 1
+PACKET_OK = 0
+PACKET_ERR_PARSE = -16
+PACKET_UNSUPPORTED = -18
+PACKET_ERR_SIGNATURE = -20
+PACKET_NOT_FOR_SELF = -21
+PACKET_MAX = 1232
+# fd_ed25519_hip_packet_plan_t
+PACKET_PLAN_DTYPE = np.dtype([("key_off", np.uint16), ("sig_off", np.uint16), ("msg0_off", np.uint16), ("msg0_sz", np.uint16),
+                              ("msg1_off", np.uint16), ("msg1_sz", np.uint16), ("disc", np.uint32)])
+_lib.fd_ed25519_hip_packet_plan.argtypes = [ctypes.c_int, ctypes.c_char_p, ctypes.c_ulong, ctypes.c_char_p, ctypes.c_void_p]
+_lib.fd_ed25519_hip_packets_dev.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_ulong] + [_u8p] * 3 + \
+    [ctypes.c_ulong, ctypes.c_char_p] + [_u8p] * 4
+_lib.fd_ed25519_hip_packets_host.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_ulong] + [_u8p] * 3 + \
+    [ctypes.c_char_p, _u8p]
+
+
+def packet_work_bytes(n, pkt_bytes):
+    """FD_ED25519_HIP_PACKET_WORK_BYTES"""
+    return 110 * int(n) + ((int(pkt_bytes) + 31) & ~15)
+
+
+def _self_key(self_key):
+    self_key = bytes(self_key)
+    if len(self_key) != 32:
+        raise ValueError("self_key must be 32 bytes")
+    return self_key
+
+
+def packet_plan(proto, pkt, self_key):
+    """fd_ed25519_hip_packet_plan: (code, plan as one PACKET_PLAN_DTYPE record)
+    of one raw packet (host only): where its key, signature and the two runs
+    of its signed message lie when the code is 0."""
+    pkt = bytes(pkt)
+    plan = np.zeros(1, PACKET_PLAN_DTYPE)
+    code = _lib.fd_ed25519_hip_packet_plan(int(proto), pkt, len(pkt), _self_key(self_key), plan.ctypes.data)
+    if code == -22:   # FD_ED25519_HIP_ERR_INVAL: an unknown protocol
+        raise ValueError("packet_plan: unknown protocol")
+    return code, plan[0]
 _lib.fd_ed25519_hip_last_error.restype = ctypes.c_char_p
 
 
@@ -329,6 +372,26 @@ class Engine:
         """Device-resident fd_ed25519_hip_shreds_dev: device addresses (ints); async."""
         _check(_lib.fd_ed25519_hip_shreds_dev(self._h, int(n), d_shreds, d_off, d_sz, d_leaders, d_work, d_out, d_roots,
                                               d_sig_out, stream))
+
+    def packets_host(self, proto, pkts, self_key):
+        """Signed gossip (PROTO_GOSSIP) or repair (PROTO_REPAIR_SERV) control
+        packets (fd_ed25519_hip_packets_host) under the validator's own
+        identity self_key -> int8 code per packet (PACKET_*); synchronous."""
+        from .tile import pack_payloads
+        n = len(pkts)
+        codes = np.zeros(n, np.int8)
+        self_key = _self_key(self_key)
+        if n:
+            buf, off, sz = pack_payloads(pkts)
+            _check(_lib.fd_ed25519_hip_packets_host(self._h, int(proto), n, _ptr(buf), _ptr(off), _ptr(sz), self_key,
+                                                    _ptr(codes)))
+        return codes
+
+    def packets_dev(self, proto, n, d_pkts, d_off, d_sz, pkt_bytes, self_key, d_work, d_out, d_sig_out=None, stream=None):
+        """Device-resident fd_ed25519_hip_packets_dev: device addresses (ints),
+        self_key 32 host bytes; async."""
+        _check(_lib.fd_ed25519_hip_packets_dev(self._h, int(proto), int(n), d_pkts, d_off, d_sz, int(pkt_bytes),
+                                               _self_key(self_key), d_work, d_out, d_sig_out, stream))
 
     def precompile_dev(self, ntxn, d_payloads, d_off, d_sz, d_ent_first, n_ent, d_work, d_txn_out, d_instr_out,
                        d_ent_out=None, stream=None):

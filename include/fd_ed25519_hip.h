@@ -211,13 +211,14 @@ typedef struct fd_ed25519_hip_engine fd_ed25519_hip_engine_t;
    the drop-in's and the pipe's host-scalar, host-decode and split-waves
    setters, latency_set_cpus; 11: Part 2b, the Ed25519 precompile
    instructions of raw transactions; 12: Part 2c, the leader signatures of
-   Merkle shreds).  A consumer checks
+   Merkle shreds; 13: Part 2d, signed gossip and repair control packets).
+   A consumer checks
    the library it loaded against the header it was built with:
    fd_ed25519_hip_abi_check( FD_ED25519_HIP_ABI_VERSION,
    sizeof(fd_ed25519_hip_slot_t), sizeof(fd_ed25519_hip_info_t),
    sizeof(fd_ed25519_hip_vservice_stats_t) ) returns 0 when they agree,
    FD_ED25519_HIP_ERR_INVAL (with fd_ed25519_hip_last_error) when not. */
-#define FD_ED25519_HIP_ABI_VERSION (12U)
+#define FD_ED25519_HIP_ABI_VERSION (13U)
 
 unsigned
 fd_ed25519_hip_abi_version( void );
@@ -660,6 +661,128 @@ fd_ed25519_hip_shreds_host( fd_ed25519_hip_engine_t * engine,
                             unsigned char const *     leaders,
                             signed char *             out,
                             unsigned char *           roots );
+
+/* ---- Part 2d: signed gossip and repair control packets ------------------ */
+
+/* A validator's gossip and repair ports take unauthenticated UDP packets;
+   for each, the reference decodes the whole bincode message and calls
+   fd_ed25519_verify before it decides whether to answer
+   (fd_gossip_recv_packet, src/flamenco/gossip/fd_gossip.c:1858, with
+   fd_gossip_handle_ping :646, _pong :912, _prune :1201;
+   fd_repair_recv_serv_packet, src/flamenco/repair/fd_repair.c:1012).  The
+   entry points below take a batch of raw packets of one protocol with the
+   validator's own identity and do that on the device for the kinds of fixed
+   or nearly fixed layout: gossip ping, pong and prune, and the repair
+   requests window_index, highest_window_index and orphan.
+
+   Per packet: one the reference's decode rejects, or that it decodes with
+   bytes left over, gets PACKET_ERR_PARSE -- and so does one of fewer than 4
+   or more than FD_ED25519_HIP_PACKET_MAX bytes (no larger UDP payload
+   reaches the reference's handlers).  A gossip pull request, pull response
+   or push message gets PACKET_UNSUPPORTED without a further look: their
+   CRDS values need the bincode walk of every fd_crds_data variant and a
+   re-encode, and stay on the caller's CPU path; so do, where they decode,
+   a repair pong (its signed message is a hash of the caller's own ping
+   token), ancestor_hashes and the seven legacy request kinds.  A prune
+   message whose destination, or a repair request whose recipient, is not
+   self_key gets PACKET_NOT_FOR_SELF: the reference drops it unverified.  A
+   judged packet that fd_ed25519_verify does not accept -- whatever its code,
+   so both code flavours agree -- gets PACKET_ERR_SIGNATURE, every other one
+   0.  A prune message is verified under data.pubkey over the bytes
+   fd_gossip_prune_sign_data_encode produces, as the reference does; a
+   gossip pong's active-table lookup and token comparison (fd_gossip.c:913-938,
+   without side effect) stay with the caller.  All five codes are this
+   library's. */
+#define FD_ED25519_HIP_PROTO_GOSSIP      (0)   /* what fd_gossip_recv_packet takes      */
+#define FD_ED25519_HIP_PROTO_REPAIR_SERV (1)   /* what fd_repair_recv_serv_packet takes */
+
+#define FD_ED25519_HIP_PACKET_OK            (  0)
+#define FD_ED25519_HIP_PACKET_ERR_PARSE     (-16)  /* the reference's decode fails or leaves bytes over */
+#define FD_ED25519_HIP_PACKET_UNSUPPORTED   (-18)  /* decodes, not judged here: the caller's CPU path  */
+#define FD_ED25519_HIP_PACKET_ERR_SIGNATURE (-20)
+#define FD_ED25519_HIP_PACKET_NOT_FOR_SELF  (-21)  /* addressed to another identity: the reference drops it unverified */
+
+#define FD_ED25519_HIP_PACKET_MAX (1232UL)         /* PACKET_DATA_SIZE, fd_gossip.c:17 */
+
+/* The rules for one packet, host only (no GPU), from the same source as the
+   device's stage kernel.  Returns 0 with the plan filled -- the key at
+   pkt[key_off..+32), the signature at pkt[sig_off..+64), the signed message
+   pkt[msg0_off..+msg0_sz) followed by pkt[msg1_off..+msg1_sz) (msg1_sz may be
+   0) -- else PACKET_ERR_PARSE, PACKET_UNSUPPORTED or PACKET_NOT_FOR_SELF
+   with every offset and size zero.  disc is the packet's discriminant
+   wherever 4 <= sz <= FD_ED25519_HIP_PACKET_MAX.  An unknown proto, a NULL
+   self_key or a NULL plan gives FD_ED25519_HIP_ERR_INVAL.  Reads pkt[0..sz)
+   only. */
+typedef struct {
+  unsigned short key_off, sig_off, msg0_off, msg0_sz, msg1_off, msg1_sz;
+  unsigned int   disc;
+} fd_ed25519_hip_packet_plan_t;
+
+int
+fd_ed25519_hip_packet_plan( int                            proto,
+                            unsigned char const *          pkt,
+                            unsigned long                  sz,
+                            unsigned char const            self_key[ 32 ],
+                            fd_ed25519_hip_packet_plan_t * plan );
+
+/* Device workspace of packets_dev for n packets in a buffer of pkt_bytes
+   bytes: per packet the gathered signature (64) and key (32), the message's
+   offset (8) and size (4), the verify code and the stage's code; and a
+   mirror of the packet buffer that holds each message at its packet's
+   place (pkt_bytes + 16, rounded up to 16). */
+#define FD_ED25519_HIP_PACKET_WORK_BYTES( n, pkt_bytes ) \
+  ( 110UL*(unsigned long)(n) + ( ( (unsigned long)(pkt_bytes) + 31UL ) & ~15UL ) )
+
+/* Device-resident batch: every pointer but the engine and self_key is a
+   device pointer.  Packet i is pkts[pkt_off[i] .. pkt_off[i] + pkt_sz[i])
+   and may start at any byte.  Packets must not overlap one another in the
+   buffer (each message is laid out at its packet's own place in the
+   workspace), and pkt_off[i] + pkt_sz[i] <= pkt_bytes: a packet that leaves
+   that range gets PACKET_ERR_PARSE and is not read.  self_key is the
+   validator's identity on the host; it travels by value in the launch.
+   out[i] receives the packet's code; sig_out (optional) fd_ed25519_verify's
+   own code for every judged packet (in the engine's code flavour) and 0 for
+   any other.  work: 16-byte aligned, FD_ED25519_HIP_PACKET_WORK_BYTES( n,
+   pkt_bytes ) bytes.
+
+   The packet buffer must start 16-byte aligned and stay readable at least
+   16 bytes past pkt_bytes (the rule of fd_ed25519_hip_verify_dev's message
+   buffer: the stage reads aligned words around unaligned bytes).
+
+   Asynchronous on `stream` (NULL: the engine's) like
+   fd_ed25519_hip_verify_dev, whose phases it runs over the n slots (chunked
+   by the engine's max_chunk): it allocates nothing beyond what that call
+   may (its second lane on an engine's first multi-chunk call) and does not
+   synchronise.  An unknown proto or a NULL self_key gives
+   FD_ED25519_HIP_ERR_INVAL; n==0 is a no-op. */
+int
+fd_ed25519_hip_packets_dev( fd_ed25519_hip_engine_t * engine,
+                            int                       proto,
+                            unsigned long             n,
+                            unsigned char const *     pkts,
+                            unsigned long const *     pkt_off,
+                            unsigned int const *      pkt_sz,
+                            unsigned long             pkt_bytes,
+                            unsigned char const       self_key[ 32 ],
+                            void *                    work,
+                            signed char *             out,
+                            signed char *             sig_out,
+                            void *                    stream );
+
+/* Host-buffer batch, synchronous: packs the packets back to back into
+   pinned staging memory (in passes, so any n fits; here packets may
+   overlap or repeat in the caller's buffer), copies, runs packets_dev on a
+   workspace the engine owns and copies out[0..n) back.  A packet of more
+   than FD_ED25519_HIP_PACKET_MAX bytes travels as its size alone. */
+int
+fd_ed25519_hip_packets_host( fd_ed25519_hip_engine_t * engine,
+                             int                       proto,
+                             unsigned long             n,
+                             unsigned char const *     pkts,
+                             unsigned long const *     pkt_off,
+                             unsigned int const *      pkt_sz,
+                             unsigned char const       self_key[ 32 ],
+                             signed char *             out );
 
 /* ---- Part 3: batched signing and the synthetic workload generator ------ */
 
