@@ -37,33 +37,7 @@
 #include <stdint.h>
 #include "../../include/fd_ed25519_hip.h"
 #include "fd_ed25519_hip_internal.h"
-
-/* dword-aligned loads around unaligned bytes (fd_ed25519_txn.hip's gather;
-   the packet buffer is readable 16 bytes past pkt_bytes) */
-__device__ static inline uint32_t load4_any(const uint8_t* src) {
-  const uintptr_t a = reinterpret_cast<uintptr_t>(src);
-  const uint32_t* w = reinterpret_cast<const uint32_t*>(a & ~(uintptr_t)3);
-  const uint32_t sh = (uint32_t)(a & 3);
-  const uint32_t d0 = w[0], d1 = sh ? w[1] : 0u;
-  return __builtin_amdgcn_alignbyte(d1, d0, sh);
-}
-
-__device__ static inline uint64_t load8_any(const uint8_t* src) {
-  const uintptr_t a = reinterpret_cast<uintptr_t>(src);
-  const uint32_t* w = reinterpret_cast<const uint32_t*>(a & ~(uintptr_t)3);
-  const uint32_t sh = (uint32_t)(a & 3);
-  const uint32_t d0 = w[0], d1 = w[1], d2 = sh ? w[2] : 0u;
-  return (uint64_t)__builtin_amdgcn_alignbyte(d1, d0, sh) | ((uint64_t)__builtin_amdgcn_alignbyte(d2, d1, sh) << 32);
-}
-
-__device__ static inline uint4 load16_any(const uint8_t* src) {
-  const uintptr_t a = reinterpret_cast<uintptr_t>(src);
-  const uint32_t* w = reinterpret_cast<const uint32_t*>(a & ~(uintptr_t)3);
-  const uint32_t sh = (uint32_t)(a & 3);
-  const uint32_t d0 = w[0], d1 = w[1], d2 = w[2], d3 = w[3], d4 = sh ? w[4] : 0u;
-  return make_uint4(__builtin_amdgcn_alignbyte(d1, d0, sh), __builtin_amdgcn_alignbyte(d2, d1, sh),
-                    __builtin_amdgcn_alignbyte(d3, d2, sh), __builtin_amdgcn_alignbyte(d4, d3, sh));
-}
+#include "fd_front_dev.h"
 
 /* 32 packet bytes against the identity in the launch's arguments */
 __device__ static inline int key_ne_any(const uint8_t* p, const uint32_t* key) {
@@ -79,14 +53,7 @@ __device__ static inline int key_ne_any(const uint8_t* p, const uint32_t* key) {
 #define FD_PACKET_KEY_NE(p, key) key_ne_any(p, key)
 #include "fd_packet_core.h"
 
-static_assert(FD_ED25519_HIP_PACKET_OK == FD_PACKET_CORE_OK && FD_ED25519_HIP_PACKET_ERR_PARSE == FD_PACKET_CORE_ERR_PARSE &&
-              FD_ED25519_HIP_PACKET_UNSUPPORTED == FD_PACKET_CORE_UNSUPPORTED &&
-              FD_ED25519_HIP_PACKET_ERR_SIGNATURE == FD_PACKET_CORE_ERR_SIGNATURE &&
-              FD_ED25519_HIP_PACKET_NOT_FOR_SELF == FD_PACKET_CORE_NOT_FOR_SELF &&
-              FD_ED25519_HIP_PROTO_GOSSIP == FD_PACKET_CORE_PROTO_GOSSIP &&
-              FD_ED25519_HIP_PROTO_REPAIR_SERV == FD_PACKET_CORE_PROTO_REPAIR_SERV &&
-              FD_ED25519_HIP_PACKET_MAX == FD_PACKET_CORE_MAX,
-              "public and core packet constants differ");
+static_assert(FD_ED25519_HIP_PACKET_OK == 0 && FD_ED25519_SUCCESS == 0, "front_verdict's zeros");
 
 /* bytes [0,k) of lo, [k,16) of hi, 0 < k < 16 */
 __device__ static inline uint32_t merge4(uint32_t lo, uint32_t hi, int k) {   /* k: bytes of lo in this dword, any int */
@@ -117,20 +84,13 @@ fd_ed25519_packet_stage_kernel(fd_ed25519_packet_stage_params_t p) {
   uint4* pk = reinterpret_cast<uint4*>(p.pubs + 32 * i);
   p.pre[i] = (int8_t)pre;
   if (pre) {
-    const uint4 z = make_uint4(0u, 0u, 0u, 0u);
-#pragma unroll
-    for (int q = 0; q < 4; q++) sg[q] = z;
-    pk[0] = z;
-    pk[1] = z;
+    FRONT_SLOT_ZERO(sg, pk);
     p.msg_off[i] = 0UL;
     p.msg_sz[i] = 0u;
     return;
   }
   const uint8_t* s = p.pkts + off;
-#pragma unroll
-  for (int q = 0; q < 4; q++) sg[q] = load16_any(s + c.sig_off + 16 * q);
-  pk[0] = load16_any(s + c.key_off);
-  pk[1] = load16_any(s + c.key_off + 16);
+  FRONT_SLOT_GATHER(sg, pk, s + c.sig_off, s + c.key_off);
 
   /* the message's place in the mirror: its first run's own place, but for a
      repair request its second run's, the discriminant 64 bytes up in front
@@ -162,22 +122,14 @@ fd_ed25519_packet_finish_kernel(fd_ed25519_packet_finish_params_t p) {
   if (i >= p.n) return;
   const int pre = p.pre[i];
   const int sig = pre ? 0 : p.codes[i];   /* a dummy slot's verify code is never read */
-  p.out[i] = (int8_t)(pre ? pre : sig != FD_ED25519_SUCCESS ? FD_ED25519_HIP_PACKET_ERR_SIGNATURE : FD_ED25519_HIP_PACKET_OK);
+  p.out[i] = (int8_t)front_verdict(pre, sig, FD_ED25519_HIP_PACKET_ERR_SIGNATURE);
   if (p.sig_out) p.sig_out[i] = (int8_t)sig;
 }
 
 extern "C" int fd_ed25519_hip_launch_packet_stage(const fd_ed25519_packet_stage_params_t* p, void* stream) {
-  if (!p->n) return 0;
-  const uint32_t blk = FD_PACKET_STAGE_BLOCK;
-  hipLaunchKernelGGL(fd_ed25519_packet_stage_kernel, dim3((uint32_t)((p->n + blk - 1) / blk)), dim3(blk), 0,
-                     (hipStream_t)stream, *p);
-  return (int)hipGetLastError();
+  return front_launch_1d(fd_ed25519_packet_stage_kernel, FD_PACKET_STAGE_BLOCK, p->n, stream, *p);
 }
 
 extern "C" int fd_ed25519_hip_launch_packet_finish(const fd_ed25519_packet_finish_params_t* p, void* stream) {
-  if (!p->n) return 0;
-  const uint32_t blk = 256;
-  hipLaunchKernelGGL(fd_ed25519_packet_finish_kernel, dim3((uint32_t)((p->n + blk - 1) / blk)), dim3(blk), 0,
-                     (hipStream_t)stream, *p);
-  return (int)hipGetLastError();
+  return front_launch_1d(fd_ed25519_packet_finish_kernel, 256, p->n, stream, *p);
 }

@@ -19,6 +19,7 @@
 #include <stdint.h>
 #include "../../include/fd_ed25519_hip.h"
 #include "fd_ed25519_hip_internal.h"
+#include "fd_front_dev.h"
 
 #define FD_SHRED_FN __device__ static inline
 #include "fd_shred_core.h"
@@ -26,22 +27,7 @@
 #define FD_DEV __device__ __forceinline__
 #include "fd_sha256_dev.h"
 
-static_assert(FD_ED25519_HIP_SHRED_OK == FD_SHRED_CORE_OK && FD_ED25519_HIP_SHRED_ERR_PARSE == FD_SHRED_CORE_ERR_PARSE &&
-              FD_ED25519_HIP_SHRED_UNSUPPORTED == FD_SHRED_CORE_UNSUPPORTED &&
-              FD_ED25519_HIP_SHRED_ERR_HEADER == FD_SHRED_CORE_ERR_HEADER &&
-              FD_ED25519_HIP_SHRED_ERR_SIGNATURE == FD_SHRED_CORE_ERR_SIGNATURE,
-              "public and core shred codes differ");
-
-/* 16 bytes at any byte address, from dword-aligned loads (fd_ed25519_txn.hip's
-   gather; the shred buffer is readable 16 bytes past every shred) */
-__device__ static inline uint4 load16_any(const uint8_t* src) {
-  const uintptr_t a = reinterpret_cast<uintptr_t>(src);
-  const uint32_t* w = reinterpret_cast<const uint32_t*>(a & ~(uintptr_t)3);
-  const uint32_t sh = (uint32_t)(a & 3);
-  const uint32_t d0 = w[0], d1 = w[1], d2 = w[2], d3 = w[3], d4 = sh ? w[4] : 0u;
-  return make_uint4(__builtin_amdgcn_alignbyte(d1, d0, sh), __builtin_amdgcn_alignbyte(d2, d1, sh),
-                    __builtin_amdgcn_alignbyte(d3, d2, sh), __builtin_amdgcn_alignbyte(d4, d3, sh));
-}
+static_assert(FD_ED25519_HIP_SHRED_OK == 0 && FD_ED25519_SUCCESS == 0, "front_verdict's zeros");
 
 /* one wave per block: a lane's work is a chain of about 30 compressions,
    and single-wave blocks spread a small batch over the most SIMDs */
@@ -59,16 +45,11 @@ fd_ed25519_shred_stage_kernel(fd_ed25519_shred_stage_params_t p) {
   p.msg_off[i] = 32 * i;
   p.pre[i] = (int8_t)pre;
   if (pre) {
-    const uint4 z = make_uint4(0u, 0u, 0u, 0u);
-#pragma unroll
-    for (int q = 0; q < 4; q++) sg[q] = z;
-    rt[0] = z;
-    rt[1] = z;
+    FRONT_SLOT_ZERO(sg, rt);   /* the key array is the caller's leaders: a zero root in the key's place */
     p.msg_sz[i] = 0u;
     return;
   }
-#pragma unroll
-  for (int q = 0; q < 4; q++) sg[q] = load16_any(s + 16 * q);
+  FRONT_SIG_GATHER(sg, s);
   uint32_t h[8];
   sha256_shred_root(h, s, c);
   rt[0] = make_uint4(__builtin_bswap32(h[0]), __builtin_bswap32(h[1]), __builtin_bswap32(h[2]), __builtin_bswap32(h[3]));
@@ -82,7 +63,7 @@ fd_ed25519_shred_finish_kernel(fd_ed25519_shred_finish_params_t p) {
   if (i >= p.n) return;
   const int pre = p.pre[i];
   const int sig = pre ? 0 : p.codes[i];   /* a dummy slot's verify code is never read */
-  p.out[i] = (int8_t)(pre ? pre : sig != FD_ED25519_SUCCESS ? FD_ED25519_HIP_SHRED_ERR_SIGNATURE : FD_ED25519_HIP_SHRED_OK);
+  p.out[i] = (int8_t)front_verdict(pre, sig, FD_ED25519_HIP_SHRED_ERR_SIGNATURE);
   if (p.sig_out) p.sig_out[i] = (int8_t)sig;
   if (p.roots_out) {
     const uint4* src = reinterpret_cast<const uint4*>(p.roots + 32 * i);
@@ -93,17 +74,9 @@ fd_ed25519_shred_finish_kernel(fd_ed25519_shred_finish_params_t p) {
 }
 
 extern "C" int fd_ed25519_hip_launch_shred_stage(const fd_ed25519_shred_stage_params_t* p, void* stream) {
-  if (!p->n) return 0;
-  const uint32_t blk = FD_SHRED_STAGE_BLOCK;
-  hipLaunchKernelGGL(fd_ed25519_shred_stage_kernel, dim3((uint32_t)((p->n + blk - 1) / blk)), dim3(blk), 0,
-                     (hipStream_t)stream, *p);
-  return (int)hipGetLastError();
+  return front_launch_1d(fd_ed25519_shred_stage_kernel, FD_SHRED_STAGE_BLOCK, p->n, stream, *p);
 }
 
 extern "C" int fd_ed25519_hip_launch_shred_finish(const fd_ed25519_shred_finish_params_t* p, void* stream) {
-  if (!p->n) return 0;
-  const uint32_t blk = 256;
-  hipLaunchKernelGGL(fd_ed25519_shred_finish_kernel, dim3((uint32_t)((p->n + blk - 1) / blk)), dim3(blk), 0,
-                     (hipStream_t)stream, *p);
-  return (int)hipGetLastError();
+  return front_launch_1d(fd_ed25519_shred_finish_kernel, 256, p->n, stream, *p);
 }

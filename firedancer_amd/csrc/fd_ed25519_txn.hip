@@ -27,6 +27,7 @@
 #include <stdint.h>
 #include "../../include/fd_ed25519_hip_tile.h"
 #include "fd_ed25519_hip_internal.h"
+#include "fd_front_dev.h"
 
 #define FD_TXN_FN __device__ static inline
 #include "fd_txn_parse_core.h"
@@ -34,18 +35,6 @@
 
 /* FD_ED25519_SUCCESS / ERR_* come from fd_ed25519_hip.h (via the tile header) */
 static_assert(FD_ED25519_TXN_PARSE_FAILED_CODE == FD_ED25519_HIP_TXN_CODE_PARSE_FAILED, "parse-failure code");
-
-/* 16 bytes at any byte address, from dword-aligned loads (the payload
-   buffer is readable 16 bytes past every payload, see the staging
-   allocation) */
-__device__ static inline uint4 load16_any(const uint8_t* src) {
-  const uintptr_t a = reinterpret_cast<uintptr_t>(src);
-  const uint32_t* w = reinterpret_cast<const uint32_t*>(a & ~(uintptr_t)3);
-  const uint32_t sh = (uint32_t)(a & 3);
-  const uint32_t d0 = w[0], d1 = w[1], d2 = w[2], d3 = w[3], d4 = sh ? w[4] : 0u;
-  return make_uint4(__builtin_amdgcn_alignbyte(d1, d0, sh), __builtin_amdgcn_alignbyte(d2, d1, sh),
-                    __builtin_amdgcn_alignbyte(d3, d2, sh), __builtin_amdgcn_alignbyte(d4, d3, sh));
-}
 
 __global__ void __launch_bounds__(256)
 fd_ed25519_txn_stage_kernel(fd_ed25519_txn_stage_params_t p) {
@@ -73,18 +62,11 @@ fd_ed25519_txn_stage_kernel(fd_ed25519_txn_stage_params_t p) {
     if (good) {
       const uint8_t* s = pay + tx.signature_off + 64u * j;
       const uint8_t* a = pay + tx.acct_addr_off + 32u * j;
-#pragma unroll
-      for (int q = 0; q < 4; q++) sg[q] = load16_any(s + 16 * q);
-      pk[0] = load16_any(a);
-      pk[1] = load16_any(a + 16);
+      FRONT_SLOT_GATHER(sg, pk, s, a);
       p.msg_off[k] = p.pay_off[t] + tx.message_off;
       p.msg_sz[k] = sz - tx.message_off;
     } else {
-      const uint4 z = make_uint4(0u, 0u, 0u, 0u);
-#pragma unroll
-      for (int q = 0; q < 4; q++) sg[q] = z;
-      pk[0] = z;
-      pk[1] = z;
+      FRONT_SLOT_ZERO(sg, pk);
       p.msg_off[k] = p.pay_off[t];
       p.msg_sz[k] = 0u;
     }
@@ -117,30 +99,18 @@ fd_ed25519_txn_finish_kernel(const int8_t* sig_codes, const uint32_t* txn_first,
 }
 
 extern "C" int fd_ed25519_hip_launch_txn_stage(const fd_ed25519_txn_stage_params_t* p, void* stream) {
-  if (!p->ntxn) return 0;
-  const uint32_t blk = 256;
-  hipLaunchKernelGGL(fd_ed25519_txn_stage_kernel, dim3((uint32_t)((p->ntxn + blk - 1) / blk)), dim3(blk), 0,
-                     (hipStream_t)stream, *p);
-  return (int)hipGetLastError();
+  return front_launch_1d(fd_ed25519_txn_stage_kernel, 256, p->ntxn, stream, *p);
 }
 
 extern "C" int fd_ed25519_hip_launch_txn_finish(const int8_t* d_sig_codes, const uint32_t* d_txn_first,
                                                 const uint32_t* d_txn_cnt, const uint8_t* d_parse_ok,
                                                 int8_t* d_txn_out, uint64_t ntxn, void* stream) {
-  if (!ntxn) return 0;
-  const uint32_t blk = 256;
-  hipLaunchKernelGGL(fd_ed25519_txn_finish_kernel, dim3((uint32_t)((ntxn + blk - 1) / blk)), dim3(blk), 0,
-                     (hipStream_t)stream, d_sig_codes, d_txn_first, d_txn_cnt, d_parse_ok, d_txn_out, ntxn);
-  return (int)hipGetLastError();
+  return front_launch_1d(fd_ed25519_txn_finish_kernel, 256, ntxn, stream, d_sig_codes, d_txn_first, d_txn_cnt, d_parse_ok,
+                         d_txn_out, ntxn);
 }
 
 /* ---- Ed25519 precompile instructions --------------------------------- */
 
-static_assert(FD_ED25519_HIP_PRECOMPILE_ERR_SIGNATURE == FD_PRECOMPILE_CORE_ERR_SIGNATURE &&
-              FD_ED25519_HIP_PRECOMPILE_ERR_DATA_OFFSET == FD_PRECOMPILE_CORE_ERR_DATA_OFFSET &&
-              FD_ED25519_HIP_PRECOMPILE_ERR_INSTR_DATA_SIZE == FD_PRECOMPILE_CORE_ERR_INSTR_DATA_SIZE,
-              "public and core precompile codes differ");
-static_assert(FD_ED25519_HIP_PRECOMPILE_ENT_MAX == FD_PRECOMPILE_CORE_ENT_MAX, "entry bound");
 /* hdr_pos and a transaction's entry count travel in a byte */
 static_assert(FD_PRECOMPILE_CORE_ENT_MAX <= 255UL, "entry counts fit a byte");
 /* the instruction table's words hold two offsets below 2^16, its mask one bit per instruction */
@@ -192,16 +162,12 @@ fd_ed25519_precompile_stage_kernel(fd_ed25519_precompile_stage_params_t p) {
   p.status[t] = (int8_t)status;
   p.hdr_instr[t] = sum.hdr_instr;
   p.hdr_pos[t] = sum.hdr_pos;
-  const uint4 z = make_uint4(0u, 0u, 0u, 0u);
   if (status) {
     for (uint32_t j = 0; j < slots; j++) {
       const uint64_t k = (uint64_t)first + j;
       uint4* sg = reinterpret_cast<uint4*>(p.sigs + 64 * k);
       uint4* pk = reinterpret_cast<uint4*>(p.pubs + 32 * k);
-#pragma unroll
-      for (int q = 0; q < 4; q++) sg[q] = z;
-      pk[0] = z;
-      pk[1] = z;
+      FRONT_SLOT_ZERO(sg, pk);
       p.msg_off[k] = base;
       p.msg_sz[k] = 0u;
       p.pre[k] = (int8_t)status;
@@ -225,15 +191,9 @@ fd_ed25519_precompile_stage_kernel(fd_ed25519_precompile_stage_params_t p) {
       if (!ent.pre) {
         const uint8_t* s = pay + ent.sig_off;
         const uint8_t* a = pay + ent.pub_off;
-#pragma unroll
-        for (int q = 0; q < 4; q++) sg[q] = load16_any(s + 16 * q);
-        pk[0] = load16_any(a);
-        pk[1] = load16_any(a + 16);
+        FRONT_SLOT_GATHER(sg, pk, s, a);
       } else {
-#pragma unroll
-        for (int q = 0; q < 4; q++) sg[q] = z;
-        pk[0] = z;
-        pk[1] = z;
+        FRONT_SLOT_ZERO(sg, pk);
       }
       p.msg_off[k] = base + ent.msg_off;
       p.msg_sz[k] = ent.msg_sz;
@@ -282,19 +242,11 @@ fd_ed25519_precompile_finish_kernel(fd_ed25519_precompile_finish_params_t p) {
 }
 
 extern "C" int fd_ed25519_hip_launch_precompile_stage(const fd_ed25519_precompile_stage_params_t* p, void* stream) {
-  if (!p->ntxn) return 0;
-  const uint32_t blk = FD_PRECOMPILE_STAGE_BLOCK;
-  hipLaunchKernelGGL(fd_ed25519_precompile_stage_kernel, dim3((uint32_t)((p->ntxn + blk - 1) / blk)), dim3(blk), 0,
-                     (hipStream_t)stream, *p);
-  return (int)hipGetLastError();
+  return front_launch_1d(fd_ed25519_precompile_stage_kernel, FD_PRECOMPILE_STAGE_BLOCK, p->ntxn, stream, *p);
 }
 
 extern "C" int fd_ed25519_hip_launch_precompile_finish(const fd_ed25519_precompile_finish_params_t* p, void* stream) {
-  if (!p->ntxn) return 0;
-  const uint32_t blk = 256;
-  hipLaunchKernelGGL(fd_ed25519_precompile_finish_kernel, dim3((uint32_t)((p->ntxn + blk - 1) / blk)), dim3(blk), 0,
-                     (hipStream_t)stream, *p);
-  return (int)hipGetLastError();
+  return front_launch_1d(fd_ed25519_precompile_finish_kernel, 256, p->ntxn, stream, *p);
 }
 
 /* fd_ed25519_hip_launch_pull (fd_ed25519_hip_internal.h): blockIdx.y picks

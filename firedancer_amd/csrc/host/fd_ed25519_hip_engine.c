@@ -25,6 +25,7 @@
 #include "../fd_precompile_core.h"
 #include "../fd_shred_core.h"
 #include "../fd_packet_core.h"
+#include "../fd_front_work.h"
 
 #include <hip/hip_runtime_api.h>
 #include <pthread.h>
@@ -98,24 +99,13 @@ struct fd_ed25519_hip_engine {
   uint32_t *   h_tfirst; uint32_t * d_tfirst;
   uint32_t *   h_tcnt;  uint32_t * d_tcnt;
   int8_t *     h_tout;  int8_t *   d_tout;
-  /* precompile_host: the per-transaction inputs (pay_off, ent_first, pay_sz)
-     and outputs (txn_out, instr_out) in one block each, and the device
-     workspace of precompile_dev */
-  uint64_t     pc_in_cap, pc_out_cap, pc_work_cap;   /* bytes */
-  uint8_t *    h_pc_in;  uint8_t *  d_pc_in;
-  uint8_t *    h_pc_out; uint8_t *  d_pc_out;
-  uint8_t *    d_pc_work;
-  /* shreds_host: a chunk's inputs (leaders, shred_off, shred_sz) and outputs
-     (roots, out) in one block each, and the device workspace of shreds_dev */
-  uint64_t     sh_in_cap, sh_out_cap, sh_work_cap;   /* bytes */
-  uint8_t *    h_sh_in;  uint8_t *  d_sh_in;
-  uint8_t *    h_sh_out; uint8_t *  d_sh_out;
-  uint8_t *    d_sh_work;
-  /* packets_host: a pass's inputs (pkt_off, pkt_sz) and the device workspace
-     of packets_dev; the codes come back through h_sh_out / d_sh_out */
-  uint64_t     pk_in_cap, pk_work_cap;               /* bytes */
-  uint8_t *    h_pk_in;  uint8_t *  d_pk_in;
-  uint8_t *    d_pk_work;
+  /* precompile_host, shreds_host, packets_host: a pass's per-item inputs and
+     its outputs in one block each, and the device workspace of the _dev call.
+     One set: the wrappers are synchronous on the engine's stream */
+  uint64_t     fr_in_cap, fr_out_cap, fr_work_cap;   /* bytes */
+  uint8_t *    h_fr_in;  uint8_t *  d_fr_in;
+  uint8_t *    h_fr_out; uint8_t *  d_fr_out;
+  uint8_t *    d_fr_work;
 
   /* per-phase event timing (bench / profiling) */
   int          timing;
@@ -403,11 +393,7 @@ engine_free( fd_ed25519_hip_engine_t * e ) {
   hipHostFree( e->h_msgs ); hipHostFree( e->h_off ); hipHostFree( e->h_sz ); hipHostFree( e->h_sigs );
   hipHostFree( e->h_pubs ); hipHostFree( e->h_out ); hipHostFree( e->h_tfirst ); hipHostFree( e->h_tcnt );
   hipHostFree( e->h_tout );
-  hipFree( e->d_pc_in ); hipFree( e->d_pc_out ); hipFree( e->d_pc_work );
-  hipHostFree( e->h_pc_in ); hipHostFree( e->h_pc_out );
-  hipFree( e->d_sh_in ); hipFree( e->d_sh_out ); hipFree( e->d_sh_work );
-  hipHostFree( e->h_sh_in ); hipHostFree( e->h_sh_out );
-  hipFree( e->d_pk_in ); hipFree( e->d_pk_work ); hipHostFree( e->h_pk_in );
+  hipFree( e->d_fr_in ); hipFree( e->d_fr_out ); hipFree( e->d_fr_work ); hipHostFree( e->h_fr_in ); hipHostFree( e->h_fr_out );
   if( e->tm_ev_init )
     for( int i=0; i<FD_ED25519_HIP_TIMING_MAX; i++ )
       for( int j=0; j<=FD_ED25519_PHASE_CNT; j++ ) hipEventDestroy( e->tm_ev[i][j] );
@@ -1357,6 +1343,91 @@ fd_ed25519_hip_verify_txns_host( fd_ed25519_hip_engine_t * e, unsigned long ntxn
   return FD_ED25519_HIP_OK;
 }
 
+/* ---- the fronts before the verify phases: stage kernel, verify_common,
+   finish kernel in a *_dev; pack, upload, *_dev, download, synchronise in a
+   *_host ("The shape of a front") ------------------------- */
+
+/* What an entry point does before any work.  Returns 1 to go on (the device
+   set, *st the call's stream), else the call's result: OK for an empty
+   batch, ERR_INVAL for a missing argument (args_ok: the caller's NULL and
+   range checks) or when one of the pointers or-ed into aligned16 (names, for
+   the message) is off a 16-byte boundary. */
+static int
+front_begin( fd_ed25519_hip_engine_t * e, unsigned long n, int args_ok, uintptr_t aligned16, char const * names,
+             void * stream, hipStream_t * st ) {
+  if( !e ) return FD_ED25519_HIP_ERR_INVAL;
+  if( !n ) return FD_ED25519_HIP_OK;
+  if( !args_ok ) return FD_ED25519_HIP_ERR_INVAL;
+  if( aligned16 & 15UL ) {
+    snprintf( fd_ed25519_hip_errbuf, sizeof(fd_ed25519_hip_errbuf), "%s must be 16-byte aligned", names );
+    return FD_ED25519_HIP_ERR_INVAL;
+  }
+  *st = stream ? (hipStream_t)stream : e->stream;
+  HIPCHK( hipSetDevice( e->device ), "hipSetDevice" );
+  return 1;
+}
+
+/* the layout the kernels are about to write against the size the caller was told to allocate */
+static int
+front_work_fits( uint64_t end, uint64_t public_bytes, char const * what ) {
+  if( end<=public_bytes ) return FD_ED25519_HIP_OK;
+  snprintf( fd_ed25519_hip_errbuf, sizeof(fd_ed25519_hip_errbuf), "%s workspace: %lu bytes laid out, %lu public", what,
+            (unsigned long)end, (unsigned long)public_bytes );
+  return FD_ED25519_HIP_ERR_INVAL;
+}
+
+/* device-only buffer grown on demand, like grow_pair */
+static int
+grow_dev( uint8_t ** d, uint64_t * cap, uint64_t need ) {
+  if( need<=*cap ) return FD_ED25519_HIP_OK;
+  uint64_t ncap = *cap ? *cap : 4096UL;
+  while( ncap<need ) ncap *= 2UL;
+  hipFree( *d ); *d = NULL; *cap = 0UL;
+  HIPCHK( hipMalloc( (void **)d, ncap ), "hipMalloc" );
+  *cap = ncap;
+  return FD_ED25519_HIP_OK;
+}
+
+/* a pass of a host wrapper: room for its item bytes (with 64 bytes behind the last) and its in and out blocks */
+static int
+front_room( fd_ed25519_hip_engine_t * e, uint64_t item_bytes, uint64_t in_bytes, uint64_t out_bytes ) {
+  int err;
+  if( (err = stage_msgs( e, item_bytes )) ) return err;
+  if( (err = grow_pair( (void **)&e->h_fr_in, (void **)&e->d_fr_in, &e->fr_in_cap, in_bytes, 1UL )) ) return err;
+  return grow_pair( (void **)&e->h_fr_out, (void **)&e->d_fr_out, &e->fr_out_cap, out_bytes, 1UL );
+}
+
+/* ... the items [off[i], off[i]+sz[i]) back to back in the pinned item staging, their places and true sizes in
+   h_off and h_sz; an item of more than cap bytes travels as its first over bytes.  Returns the bytes packed */
+static uint64_t
+front_pack( fd_ed25519_hip_engine_t * e, uint64_t m, unsigned char const * items, unsigned long const * off,
+            unsigned int const * sz, uint64_t cap, uint64_t over, uint64_t * h_off, uint32_t * h_sz ) {
+  uint64_t pos = 0UL;
+  for( uint64_t i=0UL; i<m; i++ ) {
+    uint64_t cp = sz[i]<=cap ? sz[i] : over;
+    if( cp ) memcpy( e->h_msgs + pos, items + off[i], cp );
+    h_off[i] = pos;
+    h_sz [i] = sz[i];
+    pos += cp;
+  }
+  return pos;
+}
+
+/* ... the items and the in block to the device; the out block back, with the stream drained */
+static int
+front_upload( fd_ed25519_hip_engine_t * e, uint64_t item_bytes, uint64_t in_bytes, hipStream_t st ) {
+  HIPCHK( hipMemcpyAsync( e->d_msgs, e->h_msgs, item_bytes ? item_bytes : 1UL, hipMemcpyHostToDevice, st ), "H2D front items" );
+  HIPCHK( hipMemcpyAsync( e->d_fr_in, e->h_fr_in, in_bytes, hipMemcpyHostToDevice, st ), "H2D front in" );
+  return FD_ED25519_HIP_OK;
+}
+
+static int
+front_download( fd_ed25519_hip_engine_t * e, uint64_t out_bytes, hipStream_t st ) {
+  HIPCHK( hipMemcpyAsync( e->h_fr_out, e->d_fr_out, out_bytes, hipMemcpyDeviceToHost, st ), "D2H front out" );
+  HIPCHK( hipStreamSynchronize( st ), "front" );
+  return FD_ED25519_HIP_OK;
+}
+
 /* ---- Ed25519 precompile instructions (include/fd_ed25519_hip.h Part 2b) -- */
 
 _Static_assert( FD_ED25519_HIP_PRECOMPILE_ENT_MAX==FD_PRECOMPILE_CORE_ENT_MAX, "entry bound" );
@@ -1402,105 +1473,67 @@ fd_ed25519_hip_precompile_dev( fd_ed25519_hip_engine_t * e, unsigned long ntxn, 
                                unsigned int const * ent_first, unsigned long n_ent, void * work,
                                signed char * txn_out, unsigned char * instr_out, signed char * ent_out,
                                void * stream ) {
-  if( !e ) return FD_ED25519_HIP_ERR_INVAL;
-  if( !ntxn ) return FD_ED25519_HIP_OK;
-  if( !payloads || !pay_off || !pay_sz || !ent_first || !work || !txn_out || !instr_out ||
-      n_ent>ntxn*FD_ED25519_HIP_PRECOMPILE_ENT_MAX ) return FD_ED25519_HIP_ERR_INVAL;
-  if( (uintptr_t)work & 15UL ) {
-    snprintf( fd_ed25519_hip_errbuf, sizeof(fd_ed25519_hip_errbuf), "precompile work must be 16-byte aligned" );
-    return FD_ED25519_HIP_ERR_INVAL;
-  }
-  hipStream_t st = stream ? (hipStream_t)stream : e->stream;
-  HIPCHK( hipSetDevice( e->device ), "hipSetDevice" );
-  /* FD_ED25519_HIP_PRECOMPILE_WORK_BYTES: [n_ent] sigs 64, pubs 32, msg_off
-     8, msg_sz 4, codes, pre, ent_instr 1 each; [ntxn] status, hdr_instr,
-     hdr_pos (every array aligned to its element at any n_ent) */
-  uint8_t * w = (uint8_t *)work;
-  fd_ed25519_precompile_stage_params_t sp;
-  memset( &sp, 0, sizeof(sp) );
+  hipStream_t st;
+  int err = front_begin( e, ntxn, payloads && pay_off && pay_sz && ent_first && work && txn_out && instr_out &&
+                                  n_ent<=ntxn*FD_ED25519_HIP_PRECOMPILE_ENT_MAX,
+                         (uintptr_t)work, "precompile work", stream, &st );
+  if( err<=0 ) return err;
+  front_work_t w;
+  err = front_work_fits( front_work_precompile( work, ntxn, n_ent, &w ), FD_ED25519_HIP_PRECOMPILE_WORK_BYTES( ntxn, n_ent ),
+                         "precompile" );
+  if( err ) return err;
+  fd_ed25519_precompile_stage_params_t sp = { 0 };
   sp.payloads = payloads; sp.pay_off = (uint64_t const *)pay_off; sp.pay_sz = pay_sz; sp.ent_first = ent_first;
   sp.ntxn = ntxn; sp.n_ent = n_ent;
-  sp.sigs      = w;
-  sp.pubs      = w +  64UL*n_ent;
-  sp.msg_off   = (uint64_t *)( w +  96UL*n_ent );
-  sp.msg_sz    = (uint32_t *)( w + 104UL*n_ent );
-  int8_t * codes = (int8_t *)( w + 108UL*n_ent );
-  sp.pre       = (int8_t *)( w + 109UL*n_ent );
-  sp.ent_instr = w + 110UL*n_ent;
-  sp.status    = (int8_t *)( w + 111UL*n_ent );
-  sp.hdr_instr = w + 111UL*n_ent + ntxn;
-  sp.hdr_pos   = w + 111UL*n_ent + 2UL*ntxn;
-  int err = fd_ed25519_hip_launch_precompile_stage( &sp, st );
+  sp.sigs = w.sigs; sp.pubs = w.pubs; sp.msg_off = w.msg_off; sp.msg_sz = w.msg_sz; sp.pre = w.pre;
+  sp.ent_instr = w.ent_instr; sp.status = w.status; sp.hdr_instr = w.hdr_instr; sp.hdr_pos = w.hdr_pos;
+  err = fd_ed25519_hip_launch_precompile_stage( &sp, st );
   if( err ) return hip_fail( (hipError_t)err, "precompile_stage launch" );
   if( n_ent ) {
-    err = verify_common( e, n_ent, payloads, (unsigned long const *)sp.msg_off, sp.msg_sz, NULL, sp.sigs, sp.pubs,
-                         (signed char *)codes, st );
+    err = verify_common( e, n_ent, payloads, (unsigned long const *)w.msg_off, w.msg_sz, NULL, w.sigs, w.pubs,
+                         (signed char *)w.codes, st );
     if( err ) return err;
   }
-  fd_ed25519_precompile_finish_params_t fp;
-  memset( &fp, 0, sizeof(fp) );
-  fp.codes = codes; fp.pre = sp.pre; fp.ent_instr = sp.ent_instr; fp.status = sp.status;
-  fp.hdr_instr = sp.hdr_instr; fp.hdr_pos = sp.hdr_pos; fp.ent_first = ent_first; fp.ntxn = ntxn; fp.n_ent = n_ent;
+  fd_ed25519_precompile_finish_params_t fp = { 0 };
+  fp.codes = w.codes; fp.pre = w.pre; fp.ent_instr = w.ent_instr; fp.status = w.status;
+  fp.hdr_instr = w.hdr_instr; fp.hdr_pos = w.hdr_pos; fp.ent_first = ent_first; fp.ntxn = ntxn; fp.n_ent = n_ent;
   fp.txn_out = (int8_t *)txn_out; fp.instr_out = instr_out; fp.ent_out = (int8_t *)ent_out;
   err = fd_ed25519_hip_launch_precompile_finish( &fp, st );
   if( err ) return hip_fail( (hipError_t)err, "precompile_finish launch" );
   return FD_ED25519_HIP_OK;
 }
 
-/* device-only buffer grown on demand, like grow_pair */
-static int
-grow_dev( uint8_t ** d, uint64_t * cap, uint64_t need ) {
-  if( need<=*cap ) return FD_ED25519_HIP_OK;
-  uint64_t ncap = *cap ? *cap : 4096UL;
-  while( ncap<need ) ncap *= 2UL;
-  hipFree( *d ); *d = NULL; *cap = 0UL;
-  HIPCHK( hipMalloc( (void **)d, ncap ), "hipMalloc" );
-  *cap = ncap;
-  return FD_ED25519_HIP_OK;
-}
-
+/* one pass over ntxn: the entries are counted from the packed copies, the ones the device will read */
 int
 fd_ed25519_hip_precompile_host( fd_ed25519_hip_engine_t * e, unsigned long ntxn, unsigned char const * payloads,
                                 unsigned long const * pay_off, unsigned int const * pay_sz, signed char * txn_out,
                                 unsigned char * instr_out ) {
-  if( !e ) return FD_ED25519_HIP_ERR_INVAL;
-  if( !ntxn ) return FD_ED25519_HIP_OK;
-  if( !payloads || !pay_off || !pay_sz || !txn_out || !instr_out ) return FD_ED25519_HIP_ERR_INVAL;
-  HIPCHK( hipSetDevice( e->device ), "hipSetDevice" );
+  hipStream_t st;
+  int err = front_begin( e, ntxn, payloads && pay_off && pay_sz && txn_out && instr_out, 0UL, NULL, NULL, &st );
+  if( err<=0 ) return err;
   uint64_t bytes = 0UL;
   for( uint64_t t=0UL; t<ntxn; t++ ) bytes += pay_sz[t];
   /* in: pay_off u64 [ntxn], ent_first u32 [ntxn+1], pay_sz u32 [ntxn]; out: txn_out, instr_out [ntxn] */
-  uint64_t in_bytes = 16UL*ntxn + 4UL;
-  int err;
-  if( (err = stage_msgs( e, bytes )) ) return err;   /* 64 bytes of room behind the last payload */
-  if( (err = grow_pair( (void **)&e->h_pc_in,  (void **)&e->d_pc_in,  &e->pc_in_cap,  in_bytes,  1UL )) ) return err;
-  if( (err = grow_pair( (void **)&e->h_pc_out, (void **)&e->d_pc_out, &e->pc_out_cap, 2UL*ntxn, 1UL )) ) return err;
-  uint64_t * h_off   = (uint64_t *)e->h_pc_in;
-  uint32_t * h_first = (uint32_t *)( e->h_pc_in + 8UL*ntxn );
-  uint32_t * h_sz    = h_first + ntxn + 1UL;
-  uint64_t pos = 0UL, n_ent = 0UL;
+  uint64_t in_bytes = 16UL*ntxn + 4UL, first_at = 8UL*ntxn, sz_at = 12UL*ntxn + 4UL;
+  if( (err = front_room( e, bytes, in_bytes, 2UL*ntxn )) ) return err;
+  uint64_t * h_off   = (uint64_t *)e->h_fr_in;
+  uint32_t * h_first = (uint32_t *)( e->h_fr_in + first_at );
+  front_pack( e, ntxn, payloads, pay_off, pay_sz, UINT64_MAX, 0UL, h_off, (uint32_t *)( e->h_fr_in + sz_at ) );
+  uint64_t n_ent = 0UL;
   for( uint64_t t=0UL; t<ntxn; t++ ) {
-    if( pay_sz[t] ) memcpy( e->h_msgs + pos, payloads + pay_off[t], pay_sz[t] );
-    h_off  [t] = pos;
-    h_sz   [t] = pay_sz[t];
     h_first[t] = (uint32_t)n_ent;
-    n_ent += fd_ed25519_hip_precompile_count( e->h_msgs + pos, pay_sz[t] );   /* of the copy the device will read */
-    pos   += pay_sz[t];
+    n_ent += fd_ed25519_hip_precompile_count( e->h_msgs + h_off[t], pay_sz[t] );
   }
   h_first[ntxn] = (uint32_t)n_ent;
-  if( (err = grow_dev( &e->d_pc_work, &e->pc_work_cap, FD_ED25519_HIP_PRECOMPILE_WORK_BYTES( ntxn, n_ent ) )) ) return err;
-  hipStream_t st = e->stream;
-  HIPCHK( hipMemcpyAsync( e->d_msgs, e->h_msgs, bytes ? bytes : 1UL, hipMemcpyHostToDevice, st ), "H2D payloads" );
-  HIPCHK( hipMemcpyAsync( e->d_pc_in, e->h_pc_in, in_bytes, hipMemcpyHostToDevice, st ), "H2D precompile in" );
-  uint8_t * d_out = e->d_pc_out;
-  if( (err = fd_ed25519_hip_precompile_dev( e, ntxn, e->d_msgs, (unsigned long const *)e->d_pc_in,
-                                            (unsigned int const *)( e->d_pc_in + 8UL*ntxn ) + ntxn + 1UL,
-                                            (unsigned int const *)( e->d_pc_in + 8UL*ntxn ), n_ent, e->d_pc_work,
-                                            (signed char *)d_out, d_out + ntxn, NULL, st )) ) return err;
-  HIPCHK( hipMemcpyAsync( e->h_pc_out, d_out, 2UL*ntxn, hipMemcpyDeviceToHost, st ), "D2H precompile out" );
-  HIPCHK( hipStreamSynchronize( st ), "precompile" );
-  memcpy( txn_out,   e->h_pc_out,        ntxn );
-  memcpy( instr_out, e->h_pc_out + ntxn, ntxn );
+  if( (err = grow_dev( &e->d_fr_work, &e->fr_work_cap, FD_ED25519_HIP_PRECOMPILE_WORK_BYTES( ntxn, n_ent ) )) ) return err;
+  if( (err = front_upload( e, bytes, in_bytes, st )) ) return err;
+  if( (err = fd_ed25519_hip_precompile_dev( e, ntxn, e->d_msgs, (unsigned long const *)e->d_fr_in,
+                                            (unsigned int const *)( e->d_fr_in + sz_at ),
+                                            (unsigned int const *)( e->d_fr_in + first_at ), n_ent, e->d_fr_work,
+                                            (signed char *)e->d_fr_out, e->d_fr_out + ntxn, NULL, st )) ) return err;
+  if( (err = front_download( e, 2UL*ntxn, st )) ) return err;
+  memcpy( txn_out,   e->h_fr_out,        ntxn );
+  memcpy( instr_out, e->h_fr_out + ntxn, ntxn );
   return FD_ED25519_HIP_OK;
 }
 
@@ -1523,88 +1556,26 @@ fd_ed25519_hip_shreds_dev( fd_ed25519_hip_engine_t * e, unsigned long n, unsigne
                            unsigned long const * shred_off, unsigned int const * shred_sz,
                            unsigned char const * leaders, void * work, signed char * out, unsigned char * roots,
                            signed char * sig_out, void * stream ) {
-  if( !e ) return FD_ED25519_HIP_ERR_INVAL;
-  if( !n ) return FD_ED25519_HIP_OK;
-  if( !shreds || !shred_off || !shred_sz || !leaders || !work || !out ) return FD_ED25519_HIP_ERR_INVAL;
-  if( ( (uintptr_t)work | (uintptr_t)leaders | (uintptr_t)roots | (uintptr_t)shreds ) & 15UL ) {
-    snprintf( fd_ed25519_hip_errbuf, sizeof(fd_ed25519_hip_errbuf), "shreds/leaders/work/roots must be 16-byte aligned" );
-    return FD_ED25519_HIP_ERR_INVAL;
-  }
-  hipStream_t st = stream ? (hipStream_t)stream : e->stream;
-  HIPCHK( hipSetDevice( e->device ), "hipSetDevice" );
-  /* FD_ED25519_HIP_SHRED_WORK_BYTES: [n] sigs 64, roots 32, msg_off 8, msg_sz
-     4, codes, pre 1 each (every array aligned to its element at any n; the
-     roots, being the verify messages, have the arrays behind them and the
-     16 spare bytes to be read past) */
-  uint8_t * w = (uint8_t *)work;
-  fd_ed25519_shred_stage_params_t sp;
-  memset( &sp, 0, sizeof(sp) );
+  hipStream_t st;
+  int err = front_begin( e, n, shreds && shred_off && shred_sz && leaders && work && out,
+                         (uintptr_t)work | (uintptr_t)leaders | (uintptr_t)roots | (uintptr_t)shreds,
+                         "shreds/leaders/work/roots", stream, &st );
+  if( err<=0 ) return err;
+  front_work_t w;
+  if( (err = front_work_fits( front_work_shred( work, n, &w ), FD_ED25519_HIP_SHRED_WORK_BYTES( n ), "shred" )) ) return err;
+  fd_ed25519_shred_stage_params_t sp = { 0 };
   sp.shreds = shreds; sp.shred_off = (uint64_t const *)shred_off; sp.shred_sz = shred_sz; sp.n = n;
-  sp.sigs    = w;
-  sp.roots   = w +  64UL*n;
-  sp.msg_off = (uint64_t *)( w +  96UL*n );
-  sp.msg_sz  = (uint32_t *)( w + 104UL*n );
-  int8_t * codes = (int8_t *)( w + 108UL*n );
-  sp.pre     = (int8_t *)( w + 109UL*n );
-  int err = fd_ed25519_hip_launch_shred_stage( &sp, st );
+  sp.sigs = w.sigs; sp.roots = w.pubs /* the keys are the leaders */; sp.msg_off = w.msg_off; sp.msg_sz = w.msg_sz; sp.pre = w.pre;
+  err = fd_ed25519_hip_launch_shred_stage( &sp, st );
   if( err ) return hip_fail( (hipError_t)err, "shred_stage launch" );
-  err = verify_common( e, n, sp.roots, (unsigned long const *)sp.msg_off, sp.msg_sz, NULL, sp.sigs, leaders,
-                       (signed char *)codes, st );
+  err = verify_common( e, n, w.pubs, (unsigned long const *)w.msg_off, w.msg_sz, NULL, w.sigs, leaders,
+                       (signed char *)w.codes, st );
   if( err ) return err;
-  fd_ed25519_shred_finish_params_t fp;
-  memset( &fp, 0, sizeof(fp) );
-  fp.codes = codes; fp.pre = sp.pre; fp.roots = sp.roots; fp.n = n;
+  fd_ed25519_shred_finish_params_t fp = { 0 };
+  fp.codes = w.codes; fp.pre = w.pre; fp.roots = w.pubs; fp.n = n;
   fp.out = (int8_t *)out; fp.roots_out = roots; fp.sig_out = (int8_t *)sig_out;
   err = fd_ed25519_hip_launch_shred_finish( &fp, st );
   if( err ) return hip_fail( (hipError_t)err, "shred_finish launch" );
-  return FD_ED25519_HIP_OK;
-}
-
-/* shreds per pass of shreds_host: bounds the pinned staging (20 MiB of
-   shred bytes) whatever n is */
-#define SHREDS_HOST_CHUNK 16384UL
-
-int
-fd_ed25519_hip_shreds_host( fd_ed25519_hip_engine_t * e, unsigned long n, unsigned char const * shreds,
-                            unsigned long const * shred_off, unsigned int const * shred_sz,
-                            unsigned char const * leaders, signed char * out, unsigned char * roots ) {
-  if( !e ) return FD_ED25519_HIP_ERR_INVAL;
-  if( !n ) return FD_ED25519_HIP_OK;
-  if( !shreds || !shred_off || !shred_sz || !leaders || !out ) return FD_ED25519_HIP_ERR_INVAL;
-  HIPCHK( hipSetDevice( e->device ), "hipSetDevice" );
-  hipStream_t st = e->stream;
-  int err;
-  for( uint64_t base=0UL; base<n; base+=SHREDS_HOST_CHUNK ) {
-    uint64_t m = n-base<SHREDS_HOST_CHUNK ? n-base : SHREDS_HOST_CHUNK;
-    /* in: leaders 32 [m], shred_off u64 [m], shred_sz u32 [m]; out: roots 32 [m], out [m] */
-    if( (err = stage_msgs( e, m*FD_SHRED_CORE_MAX_SZ )) ) return err;   /* 64 bytes of room behind the last shred */
-    if( (err = grow_pair( (void **)&e->h_sh_in,  (void **)&e->d_sh_in,  &e->sh_in_cap,  44UL*m, 1UL )) ) return err;
-    if( (err = grow_pair( (void **)&e->h_sh_out, (void **)&e->d_sh_out, &e->sh_out_cap, 33UL*m, 1UL )) ) return err;
-    if( (err = grow_dev( &e->d_sh_work, &e->sh_work_cap, FD_ED25519_HIP_SHRED_WORK_BYTES( m ) )) ) return err;
-    uint64_t * h_off = (uint64_t *)( e->h_sh_in + 32UL*m );
-    uint32_t * h_sz  = (uint32_t *)( e->h_sh_in + 40UL*m );
-    memcpy( e->h_sh_in, leaders + 32UL*base, 32UL*m );
-    uint64_t pos = 0UL;
-    for( uint64_t i=0UL; i<m; i++ ) {
-      /* no rule reads a byte at or past FD_SHRED_MAX_SZ, so a longer shred
-         travels as its head and its true size */
-      uint64_t sz = shred_sz[base+i], cp = sz<FD_SHRED_CORE_MAX_SZ ? sz : FD_SHRED_CORE_MAX_SZ;
-      if( cp ) memcpy( e->h_msgs + pos, shreds + shred_off[base+i], cp );
-      h_off[i] = pos;
-      h_sz [i] = (uint32_t)sz;
-      pos += cp;
-    }
-    HIPCHK( hipMemcpyAsync( e->d_msgs, e->h_msgs, pos ? pos : 1UL, hipMemcpyHostToDevice, st ), "H2D shreds" );
-    HIPCHK( hipMemcpyAsync( e->d_sh_in, e->h_sh_in, 44UL*m, hipMemcpyHostToDevice, st ), "H2D shreds in" );
-    if( (err = fd_ed25519_hip_shreds_dev( e, m, e->d_msgs, (unsigned long const *)( e->d_sh_in + 32UL*m ),
-                                          (unsigned int const *)( e->d_sh_in + 40UL*m ), e->d_sh_in, e->d_sh_work,
-                                          (signed char *)( e->d_sh_out + 32UL*m ), roots ? e->d_sh_out : NULL, NULL,
-                                          st )) ) return err;
-    HIPCHK( hipMemcpyAsync( e->h_sh_out, e->d_sh_out, 33UL*m, hipMemcpyDeviceToHost, st ), "D2H shreds out" );
-    HIPCHK( hipStreamSynchronize( st ), "shreds" );
-    memcpy( out + base, e->h_sh_out + 32UL*m, m );
-    if( roots ) memcpy( roots + 32UL*base, e->h_sh_out, 32UL*m );
-  }
   return FD_ED25519_HIP_OK;
 }
 
@@ -1641,89 +1612,95 @@ fd_ed25519_hip_packets_dev( fd_ed25519_hip_engine_t * e, int proto, unsigned lon
                             unsigned long const * pkt_off, unsigned int const * pkt_sz, unsigned long pkt_bytes,
                             unsigned char const self_key[ 32 ], void * work, signed char * out, signed char * sig_out,
                             void * stream ) {
-  if( !e || !packet_proto_ok( proto ) || !self_key ) return FD_ED25519_HIP_ERR_INVAL;
-  if( !n ) return FD_ED25519_HIP_OK;
-  if( !pkts || !pkt_off || !pkt_sz || !work || !out ) return FD_ED25519_HIP_ERR_INVAL;
-  if( ( (uintptr_t)work | (uintptr_t)pkts ) & 15UL ) {
-    snprintf( fd_ed25519_hip_errbuf, sizeof(fd_ed25519_hip_errbuf), "pkts/work must be 16-byte aligned" );
-    return FD_ED25519_HIP_ERR_INVAL;
-  }
-  hipStream_t st = stream ? (hipStream_t)stream : e->stream;
-  HIPCHK( hipSetDevice( e->device ), "hipSetDevice" );
-  /* FD_ED25519_HIP_PACKET_WORK_BYTES: [n] sigs 64, pubs 32, then the mirror
-     of the packet buffer (pkt_bytes + 16 rounded up to 16: the messages,
-     with the 16 spare bytes to be read past), then [n] msg_off 8, msg_sz 4,
-     codes, pre 1 each (every array aligned to its element at any n) */
-  uint8_t * w = (uint8_t *)work;
-  uint64_t  mirror = ( (uint64_t)pkt_bytes + 31UL ) & ~15UL;
-  fd_ed25519_packet_stage_params_t sp;
-  memset( &sp, 0, sizeof(sp) );
+  if( !packet_proto_ok( proto ) || !self_key ) return FD_ED25519_HIP_ERR_INVAL;   /* of an empty batch too */
+  hipStream_t st;
+  int err = front_begin( e, n, pkts && pkt_off && pkt_sz && work && out, (uintptr_t)work | (uintptr_t)pkts, "pkts/work",
+                         stream, &st );
+  if( err<=0 ) return err;
+  front_work_t w;
+  err = front_work_fits( front_work_packet( work, n, pkt_bytes, &w ), FD_ED25519_HIP_PACKET_WORK_BYTES( n, pkt_bytes ),
+                         "packet" );
+  if( err ) return err;
+  fd_ed25519_packet_stage_params_t sp = { 0 };
   sp.pkts = pkts; sp.pkt_off = (uint64_t const *)pkt_off; sp.pkt_sz = pkt_sz; sp.n = n; sp.pkt_bytes = pkt_bytes;
   memcpy( sp.self_key, self_key, 32UL );
-  sp.proto   = proto;
-  sp.sigs    = w;
-  sp.pubs    = w +  64UL*n;
-  sp.msgs    = w +  96UL*n;
-  sp.msg_off = (uint64_t *)( w +  96UL*n + mirror );
-  sp.msg_sz  = (uint32_t *)( w + 104UL*n + mirror );
-  int8_t * codes = (int8_t *)( w + 108UL*n + mirror );
-  sp.pre     = (int8_t *)( w + 109UL*n + mirror );
-  int err = fd_ed25519_hip_launch_packet_stage( &sp, st );
+  sp.proto = proto;
+  sp.sigs = w.sigs; sp.pubs = w.pubs; sp.msgs = w.msgs; sp.msg_off = w.msg_off; sp.msg_sz = w.msg_sz; sp.pre = w.pre;
+  err = fd_ed25519_hip_launch_packet_stage( &sp, st );
   if( err ) return hip_fail( (hipError_t)err, "packet_stage launch" );
-  err = verify_common( e, n, sp.msgs, (unsigned long const *)sp.msg_off, sp.msg_sz, NULL, sp.sigs, sp.pubs,
-                       (signed char *)codes, st );
+  err = verify_common( e, n, w.msgs, (unsigned long const *)w.msg_off, w.msg_sz, NULL, w.sigs, w.pubs,
+                       (signed char *)w.codes, st );
   if( err ) return err;
-  fd_ed25519_packet_finish_params_t fp;
-  memset( &fp, 0, sizeof(fp) );
-  fp.codes = codes; fp.pre = sp.pre; fp.n = n; fp.out = (int8_t *)out; fp.sig_out = (int8_t *)sig_out;
+  fd_ed25519_packet_finish_params_t fp = { 0 };
+  fp.codes = w.codes; fp.pre = w.pre; fp.n = n; fp.out = (int8_t *)out; fp.sig_out = (int8_t *)sig_out;
   err = fd_ed25519_hip_launch_packet_finish( &fp, st );
   if( err ) return hip_fail( (hipError_t)err, "packet_finish launch" );
   return FD_ED25519_HIP_OK;
 }
 
-/* packets per pass of packets_host: bounds the pinned staging (20 MiB of
-   packet bytes) whatever n is */
-#define PACKETS_HOST_CHUNK 16384UL
+/* ---- shreds_host and packets_host ---------------------------------------- */
+
+/* items per pass: bounds the pinned staging (20 MiB of item bytes) whatever n is */
+#define FRONT_HOST_CHUNK 16384UL
+
+/* The round trip of shreds (leaders given) and of packets (leaders NULL),
+   pass by pass.  A shred pass has the leaders, 32 bytes each, in front of
+   its in block (off u64 [m], sz u32 [m]) and the roots, 32 bytes each, in
+   front of its out block (codes [m]).  No shred rule reads a byte at or past
+   FD_SHRED_MAX_SZ, so a longer shred travels as its head and its true size;
+   no packet rule reads a packet of more than FD_ED25519_HIP_PACKET_MAX bytes
+   at all: it travels as its true size alone, and leaves the packed range. */
+static int
+front_items_host( fd_ed25519_hip_engine_t * e, hipStream_t st, unsigned long n, unsigned char const * items,
+                  unsigned long const * off, unsigned int const * sz, unsigned char const * leaders, int proto,
+                  unsigned char const * self_key, signed char * out, unsigned char * roots ) {
+  uint64_t cap  = leaders ? FD_SHRED_CORE_MAX_SZ : FD_PACKET_CORE_MAX, over = leaders ? cap : 0UL;
+  uint64_t lead = leaders ? 32UL : 0UL;
+  int err;
+  for( uint64_t base=0UL; base<n; base+=FRONT_HOST_CHUNK ) {
+    uint64_t m = n-base<FRONT_HOST_CHUNK ? n-base : FRONT_HOST_CHUNK;
+    uint64_t off_at = lead*m, sz_at = off_at + 8UL*m, in_bytes = sz_at + 4UL*m, out_bytes = lead*m + m;
+    if( (err = front_room( e, m*cap, in_bytes, out_bytes )) ) return err;
+    if( leaders ) memcpy( e->h_fr_in, leaders + 32UL*base, 32UL*m );
+    uint64_t pos = front_pack( e, m, items, off+base, sz+base, cap, over, (uint64_t *)( e->h_fr_in + off_at ),
+                               (uint32_t *)( e->h_fr_in + sz_at ) );
+    uint64_t work = leaders ? FD_ED25519_HIP_SHRED_WORK_BYTES( m ) : FD_ED25519_HIP_PACKET_WORK_BYTES( m, pos );
+    if( (err = grow_dev( &e->d_fr_work, &e->fr_work_cap, work )) ) return err;
+    if( (err = front_upload( e, pos, in_bytes, st )) ) return err;
+    unsigned long const * d_off   = (unsigned long const *)( e->d_fr_in + off_at );
+    unsigned int const *  d_sz    = (unsigned int const *)( e->d_fr_in + sz_at );
+    signed char *         d_codes = (signed char *)( e->d_fr_out + lead*m );
+    err = leaders ? fd_ed25519_hip_shreds_dev( e, m, e->d_msgs, d_off, d_sz, e->d_fr_in, e->d_fr_work, d_codes,
+                                               roots ? e->d_fr_out : NULL, NULL, st )
+                  : fd_ed25519_hip_packets_dev( e, proto, m, e->d_msgs, d_off, d_sz, pos, self_key, e->d_fr_work, d_codes,
+                                                NULL, st );
+    if( err ) return err;
+    if( (err = front_download( e, out_bytes, st )) ) return err;
+    memcpy( out + base, e->h_fr_out + lead*m, m );
+    if( roots ) memcpy( roots + 32UL*base, e->h_fr_out, 32UL*m );
+  }
+  return FD_ED25519_HIP_OK;
+}
+
+int
+fd_ed25519_hip_shreds_host( fd_ed25519_hip_engine_t * e, unsigned long n, unsigned char const * shreds,
+                            unsigned long const * shred_off, unsigned int const * shred_sz,
+                            unsigned char const * leaders, signed char * out, unsigned char * roots ) {
+  hipStream_t st;
+  int err = front_begin( e, n, shreds && shred_off && shred_sz && leaders && out, 0UL, NULL, NULL, &st );
+  if( err<=0 ) return err;
+  return front_items_host( e, st, n, shreds, shred_off, shred_sz, leaders, 0, NULL, out, roots );
+}
 
 int
 fd_ed25519_hip_packets_host( fd_ed25519_hip_engine_t * e, int proto, unsigned long n, unsigned char const * pkts,
                              unsigned long const * pkt_off, unsigned int const * pkt_sz,
                              unsigned char const self_key[ 32 ], signed char * out ) {
-  if( !e || !packet_proto_ok( proto ) || !self_key ) return FD_ED25519_HIP_ERR_INVAL;
-  if( !n ) return FD_ED25519_HIP_OK;
-  if( !pkts || !pkt_off || !pkt_sz || !out ) return FD_ED25519_HIP_ERR_INVAL;
-  HIPCHK( hipSetDevice( e->device ), "hipSetDevice" );
-  hipStream_t st = e->stream;
-  int err;
-  for( uint64_t base=0UL; base<n; base+=PACKETS_HOST_CHUNK ) {
-    uint64_t m = n-base<PACKETS_HOST_CHUNK ? n-base : PACKETS_HOST_CHUNK;
-    /* in: pkt_off u64 [m], pkt_sz u32 [m]; out: out [m] */
-    if( (err = stage_msgs( e, m*FD_PACKET_CORE_MAX )) ) return err;   /* 64 bytes of room behind the last packet */
-    if( (err = grow_pair( (void **)&e->h_pk_in,  (void **)&e->d_pk_in,  &e->pk_in_cap,  12UL*m, 1UL )) ) return err;
-    if( (err = grow_pair( (void **)&e->h_sh_out, (void **)&e->d_sh_out, &e->sh_out_cap, m,      1UL )) ) return err;
-    uint64_t * h_off = (uint64_t *)e->h_pk_in;
-    uint32_t * h_sz  = (uint32_t *)( e->h_pk_in + 8UL*m );
-    uint64_t pos = 0UL;
-    for( uint64_t i=0UL; i<m; i++ ) {
-      /* no rule reads a packet of more than FD_ED25519_HIP_PACKET_MAX bytes:
-         it travels as its true size alone, and leaves the packed range */
-      uint64_t sz = pkt_sz[base+i], cp = sz<=FD_PACKET_CORE_MAX ? sz : 0UL;
-      if( cp ) memcpy( e->h_msgs + pos, pkts + pkt_off[base+i], cp );
-      h_off[i] = pos;
-      h_sz [i] = (uint32_t)sz;
-      pos += cp;
-    }
-    if( (err = grow_dev( &e->d_pk_work, &e->pk_work_cap, FD_ED25519_HIP_PACKET_WORK_BYTES( m, pos ) )) ) return err;
-    HIPCHK( hipMemcpyAsync( e->d_msgs, e->h_msgs, pos ? pos : 1UL, hipMemcpyHostToDevice, st ), "H2D packets" );
-    HIPCHK( hipMemcpyAsync( e->d_pk_in, e->h_pk_in, 12UL*m, hipMemcpyHostToDevice, st ), "H2D packets in" );
-    if( (err = fd_ed25519_hip_packets_dev( e, proto, m, e->d_msgs, (unsigned long const *)e->d_pk_in,
-                                           (unsigned int const *)( e->d_pk_in + 8UL*m ), pos, self_key, e->d_pk_work,
-                                           (signed char *)e->d_sh_out, NULL, st )) ) return err;
-    HIPCHK( hipMemcpyAsync( e->h_sh_out, e->d_sh_out, m, hipMemcpyDeviceToHost, st ), "D2H packets out" );
-    HIPCHK( hipStreamSynchronize( st ), "packets" );
-    memcpy( out + base, e->h_sh_out, m );
-  }
-  return FD_ED25519_HIP_OK;
+  if( !packet_proto_ok( proto ) || !self_key ) return FD_ED25519_HIP_ERR_INVAL;
+  hipStream_t st;
+  int err = front_begin( e, n, pkts && pkt_off && pkt_sz && out, 0UL, NULL, NULL, &st );
+  if( err<=0 ) return err;
+  return front_items_host( e, st, n, pkts, pkt_off, pkt_sz, NULL, proto, self_key, out, NULL );
 }
 
 /* ---- drop-in API -------------------------------------------------------

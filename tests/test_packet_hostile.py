@@ -3,13 +3,12 @@ compiled with a stand-alone main (tests/packet_walk_main.c) under ASan and
 UBSan, run on the reference-judged fixture, rule-edge, mutated and truncated
 packets held in heap blocks of exactly their size.  A program of its own:
 nothing is loaded into this interpreter."""
-import os
 import struct
 import subprocess
 
 import pytest
 
-from conftest import REPO
+import san_build
 from packet_util import Node, fixture, mutated, rule_cases, valid_packets
 
 FIELDS = ("disc", "key_off", "sig_off", "msg0_off", "msg0_sz", "msg1_off", "msg1_sz")
@@ -17,14 +16,7 @@ FIELDS = ("disc", "key_off", "sig_off", "msg0_off", "msg0_sz", "msg1_off", "msg1
 
 @pytest.fixture(scope="module")
 def walker(tmp_path_factory):
-    exe = tmp_path_factory.mktemp("packet_walk") / "packet_walk"
-    r = subprocess.run(["gcc", "-std=c11", "-O1", "-g", "-Wall", "-Wextra", "-Werror", "-fsanitize=address,undefined",
-                        "-fno-sanitize-recover=all", "-fno-omit-frame-pointer", "-static-libasan", "-static-libubsan",
-                        "-I" + os.path.join(REPO, "firedancer_amd", "csrc"),
-                        os.path.join(REPO, "tests", "packet_walk_main.c"), "-o", str(exe)],
-                       capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr
-    return str(exe)
+    return san_build.build("packet_walk_main.c", tmp_path_factory.mktemp("packet_walk") / "packet_walk")
 
 
 def test_walk_of_hostile_packets_is_clean_and_agrees_with_the_library(walker, oracle, tmp_path):

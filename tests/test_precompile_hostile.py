@@ -3,27 +3,18 @@ fd_txn_parse_core.h compiled with a stand-alone main
 (tests/precompile_walk_main.c) under ASan and UBSan, run on mutated
 precompile transactions held in heap blocks of exactly their size.  A
 program of its own: nothing is loaded into this interpreter."""
-import os
 import struct
 import subprocess
 
 import pytest
 
-from conftest import REPO
+import san_build
 from precompile_util import max_entries_txn, mutated, rule_cases
 
 
 @pytest.fixture(scope="module")
 def walker(tmp_path_factory):
-    exe = tmp_path_factory.mktemp("precompile_walk") / "precompile_walk"
-    r = subprocess.run(["gcc", "-std=c11", "-O1", "-g", "-Wall", "-Wextra", "-Werror", "-fsanitize=address,undefined",
-                        "-fno-sanitize-recover=all", "-fno-omit-frame-pointer", "-static-libasan", "-static-libubsan",
-                        "-I" + os.path.join(REPO, "include"),
-                        "-I" + os.path.join(REPO, "firedancer_amd", "csrc"),
-                        os.path.join(REPO, "tests", "precompile_walk_main.c"), "-o", str(exe)],
-                       capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr
-    return str(exe)
+    return san_build.build("precompile_walk_main.c", tmp_path_factory.mktemp("precompile_walk") / "precompile_walk")
 
 
 def test_walk_of_hostile_payloads_is_clean_and_agrees_with_the_library(walker, oracle, tmp_path):

@@ -2,26 +2,18 @@
 stand-alone main (tests/shred_walk_main.c) under ASan and UBSan, run on
 mutated, rule-edge and truncated shreds held in heap blocks of exactly their
 size.  A program of its own: nothing is loaded into this interpreter."""
-import os
 import struct
 import subprocess
 
 import pytest
 
-from conftest import REPO
+import san_build
 from shred_util import every_depth, fixture, mutated, rule_cases
 
 
 @pytest.fixture(scope="module")
 def walker(tmp_path_factory):
-    exe = tmp_path_factory.mktemp("shred_walk") / "shred_walk"
-    r = subprocess.run(["gcc", "-std=c11", "-O1", "-g", "-Wall", "-Wextra", "-Werror", "-fsanitize=address,undefined",
-                        "-fno-sanitize-recover=all", "-fno-omit-frame-pointer", "-static-libasan", "-static-libubsan",
-                        "-I" + os.path.join(REPO, "firedancer_amd", "csrc"),
-                        os.path.join(REPO, "tests", "shred_walk_main.c"), "-o", str(exe)],
-                       capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr
-    return str(exe)
+    return san_build.build("shred_walk_main.c", tmp_path_factory.mktemp("shred_walk") / "shred_walk")
 
 
 def test_walk_of_hostile_shreds_is_clean_and_agrees_with_the_library(walker, oracle, tmp_path):
