@@ -519,6 +519,56 @@ typedef struct {
 int fd_ed25519_hip_launch_packet_stage( fd_ed25519_packet_stage_params_t const * p, void * stream );
 int fd_ed25519_hip_launch_packet_finish( fd_ed25519_packet_finish_params_t const * p, void * stream );
 
+/* ---- CRDS values of gossip pull responses and push messages (fd_ed25519_crds.hip) ---- */
+
+/* stage: one lane per packet walks it by fd_crds_core.h's rules and fills
+   the slots [val_first[i], val_first[i+1]) -- never one outside them --
+   with each value's signature and key, its message left in place in the
+   packet buffer; a dummy (zero signature and key, msg_sz 0) for a value
+   under the own identity and for every slot of a packet without verdicts */
+typedef struct {
+  uint8_t const *  pkts;       /* 4-B aligned, readable 16 B past pkt_bytes  */
+  uint64_t const * pkt_off;    /* [n]                                        */
+  uint32_t const * pkt_sz;     /* [n]                                        */
+  uint32_t const * val_first;  /* [n+1] the caller's reservation             */
+  uint64_t         n;
+  uint64_t         n_val;
+  uint64_t         pkt_bytes;
+  uint32_t         self_key[ 8 ];  /* the own identity, by value             */
+  uint8_t *        sigs;       /* [n_val][64] out, 16-B aligned              */
+  uint8_t *        pubs;       /* [n_val][32] out, 16-B aligned              */
+  uint64_t *       msg_off;    /* [n_val] out, into pkts                     */
+  uint32_t *       msg_sz;     /* [n_val] out                                */
+  uint32_t *       val_sz;     /* [n_val] out: the data's size; 0: no hash   */
+  int8_t *         pre;        /* [n_val] out: 0, OWN, or the packet's code  */
+  int8_t *         status;     /* [n] out: 0, ERR_PARSE, UNSUPPORTED, BAD_RESERVATION */
+} fd_ed25519_crds_stage_params_t;
+
+/* finish: lane k < n_val the value's verdict, lane i < n the packet's code */
+typedef struct {
+  int8_t const *   codes;      /* [n_val] the verify phases' codes           */
+  int8_t const *   pre;
+  int8_t const *   status;
+  uint64_t         n;
+  uint64_t         n_val;
+  int8_t *         pkt_out;    /* [n]                                        */
+  int8_t *         val_out;    /* [n_val]                                    */
+  int8_t *         sig_out;    /* [n_val] or NULL                            */
+} fd_ed25519_crds_finish_params_t;
+
+/* hash: one lane per value, SHA-256 of pkts[msg_off-64 .. msg_off+val_sz) */
+typedef struct {
+  uint8_t const *  pkts;
+  uint64_t const * msg_off;
+  uint32_t const * val_sz;
+  uint64_t         n_val;
+  uint8_t *        hash_out;   /* [n_val][32], 4-B aligned                   */
+} fd_ed25519_crds_hash_params_t;
+
+int fd_ed25519_hip_launch_crds_stage( fd_ed25519_crds_stage_params_t const * p, void * stream );
+int fd_ed25519_hip_launch_crds_finish( fd_ed25519_crds_finish_params_t const * p, void * stream );
+int fd_ed25519_hip_launch_crds_hash( fd_ed25519_crds_hash_params_t const * p, void * stream );
+
 /* ---- generator (fd_ed25519_gen.hip) ---- */
 
 typedef struct {

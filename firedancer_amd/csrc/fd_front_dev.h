@@ -1,6 +1,7 @@
 /* fd_front_dev.h -- what the stage and finish kernels of the fronts before
    the verify phases share (fd_ed25519_txn.hip, fd_ed25519_shred.hip,
-   fd_ed25519_packet.hip; DESIGN.md 3a, "The shape of a front"). */
+   fd_ed25519_packet.hip, fd_ed25519_crds.hip; DESIGN.md 3a, "The shape of a
+   front"). */
 #ifndef FD_FRONT_DEV_H
 #define FD_FRONT_DEV_H
 

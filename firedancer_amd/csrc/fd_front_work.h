@@ -1,10 +1,10 @@
 /* fd_front_work.h -- the device workspace of the fronts before the verify
-   phases (fd_ed25519_hip_precompile_dev, _shreds_dev, _packets_dev), carved
+   phases (fd_ed25519_hip_precompile_dev, _shreds_dev, _packets_dev, _crds_dev), carved
    out of the caller's 16-byte-aligned buffer.  Plain C11, host only, nothing
    but pointer arithmetic: the engine (host/fd_ed25519_hip_engine.c) takes
-   its kernels' arrays from here, and tests/front_work_main.c holds every
-   layout to the public FD_ED25519_HIP_*_WORK_BYTES macro a caller sizes the
-   buffer with.  A layout has no padding: the elements only get smaller, so
+   its kernels' arrays from here, and tests/front_work_main.c (the CRDS
+   front's: tests/crds_work_main.c) holds every layout to the public
+   FD_ED25519_HIP_*_WORK_BYTES macro a caller sizes the buffer with.  A layout has no padding: the elements only get smaller, so
    every array is aligned to its element at any count. */
 #ifndef FD_FRONT_WORK_H
 #define FD_FRONT_WORK_H
@@ -32,6 +32,7 @@ typedef struct {      /* in the buffer's order; [n] slots */
   int8_t *   status;                          /* and [ntxn] from here                          */
   uint8_t *  hdr_instr;
   uint8_t *  hdr_pos;
+  uint32_t * val_sz;                          /* the CRDS front's: [n_val], the size of a value's data */
 } front_work_t;
 
 /* what every layout begins with */
@@ -69,6 +70,24 @@ front_work_shred( void * work, uint64_t n, front_work_t * w ) {
 static inline uint64_t
 front_work_packet( void * work, uint64_t n, uint64_t pkt_bytes, front_work_t * w ) {
   return (uint64_t)( front_work_slots( work, n, ( pkt_bytes + 31UL ) & ~15UL, w ) - (uint8_t *)work );
+}
+
+/* The CRDS front keeps a 4-byte array more per slot (val_sz), which has to
+   stand ahead of the 1-byte ones, so it carves its slots itself; its
+   messages are read in place.  status: [n], the packets' codes. */
+static inline uint64_t
+front_work_crds( void * work, uint64_t n, uint64_t n_val, front_work_t * w ) {
+  uint8_t * c = (uint8_t *)work;
+  *w = (front_work_t){ 0 };
+  w->sigs    = (uint8_t *) front_carve( &c, n_val, 64UL );
+  w->pubs    = (uint8_t *) front_carve( &c, n_val, 32UL );
+  w->msg_off = (uint64_t *)front_carve( &c, n_val, 8UL );
+  w->msg_sz  = (uint32_t *)front_carve( &c, n_val, 4UL );
+  w->val_sz  = (uint32_t *)front_carve( &c, n_val, 4UL );
+  w->codes   = (int8_t *)  front_carve( &c, n_val, 1UL );
+  w->pre     = (int8_t *)  front_carve( &c, n_val, 1UL );
+  w->status  = (int8_t *)  front_carve( &c, n,     1UL );
+  return (uint64_t)( c - (uint8_t *)work );
 }
 
 #endif /* FD_FRONT_WORK_H */

@@ -189,4 +189,89 @@ fd_txn_core_parse( unsigned char const * p, unsigned long sz, fd_ed25519_hip_txn
   return foot;
 }
 
+/* The prefix form: fd_txn_parse_core with a size out-parameter
+   (payload_sz_opt != NULL, src/ballet/txn/fd_txn_parse.c:222, :238), as
+   fd_flamenco_txn_decode_preflight calls it on the bytes that remain of a
+   bincode message (src/flamenco/types/fd_types_custom.c:28-38): the same
+   rules as fd_txn_core_parse but for "every byte consumed", so bytes may
+   follow the transaction.  Returns the bytes the transaction takes (0:
+   rejected); it writes nothing.  avail is all that remains, the
+   transaction's bytes and what follows: a compact-u16 is decoded against
+   it, as the reference's READ_CHECKED_COMPACT_U16 is (:71). */
+FD_TXN_FN unsigned long
+fd_txn_core_parse_prefix( unsigned char const * p, unsigned long avail ) {
+  unsigned long i = 0UL, n;
+  unsigned v;
+#define HAVE( k ) ( (unsigned long)(k) <= avail - i )
+#define CU16( dst ) do { n = fd_txn_core_cu16( p + i, avail - i, &v ); if( !n ) return 0; (dst) = v; i += n; } while(0)
+  if( avail>FD_TXN_CORE_MTU ) return 0;                                                  /* :80 */
+  if( !HAVE( 1 ) ) return 0;
+  unsigned sig_cnt = p[ i++ ];
+  if( sig_cnt<1U || sig_cnt>FD_TXN_CORE_SIG_MAX ) return 0;                              /* :89 */
+  if( !HAVE( 64UL*sig_cnt ) ) return 0;
+  i += 64UL*sig_cnt;
+  if( !HAVE( 1 ) ) return 0;
+  unsigned b0 = p[ i++ ];
+  int v0 = 0;
+  if( b0 & 0x80U ) {
+    if( ( b0 & 0x7FU )!=0U ) return 0;
+    v0 = 1;
+    if( !HAVE( 1 ) ) return 0;
+    if( p[ i ]!=sig_cnt ) return 0;
+    i++;
+  } else if( b0!=sig_cnt ) return 0;
+  if( !HAVE( 1 ) ) return 0;
+  unsigned ro_signed = p[ i++ ];
+  if( !(ro_signed<sig_cnt) ) return 0;                                                   /* :108 */
+  if( !HAVE( 1 ) ) return 0;
+  unsigned ro_unsigned = p[ i++ ];
+  unsigned acct_cnt;  CU16( acct_cnt );
+  if( !(sig_cnt<=acct_cnt && acct_cnt<=FD_TXN_CORE_ACCT_MAX) ) return 0;
+  if( sig_cnt + ro_unsigned > acct_cnt ) return 0;
+  if( !HAVE( 32UL*acct_cnt ) ) return 0;
+  i += 32UL*acct_cnt;
+  if( !HAVE( 32 ) ) return 0;
+  i += 32UL;
+  unsigned instr_cnt;  CU16( instr_cnt );
+  if( instr_cnt>FD_TXN_CORE_INSTR_MAX ) return 0;
+  if( !HAVE( 3UL*instr_cnt ) ) return 0;
+  if( !(acct_cnt > (instr_cnt ? 1U : 0U)) ) return 0;                                    /* :129 */
+  unsigned max_acct = 0U;
+  for( unsigned j=0U; j<instr_cnt; j++ ) {
+    if( !HAVE( 3 ) ) return 0;
+    unsigned prog = p[ i++ ];
+    unsigned ia; CU16( ia );
+    if( !HAVE( ia ) ) return 0;
+    for( unsigned k=0U; k<ia; k++ ) if( p[ i+k ]>max_acct ) max_acct = p[ i+k ];
+    i += ia;
+    unsigned dsz; CU16( dsz );
+    if( !HAVE( dsz ) ) return 0;
+    i += dsz;
+    if( !(0U<prog && prog<acct_cnt) ) return 0;                                          /* :168 */
+  }
+  unsigned long adtl = 0UL;
+  if( v0 ) {
+    unsigned lut_cnt;  CU16( lut_cnt );
+    if( lut_cnt>FD_TXN_CORE_LUT_MAX ) return 0;
+    if( !HAVE( 34UL*lut_cnt ) ) return 0;
+    for( unsigned j=0U; j<lut_cnt; j++ ) {
+      if( !HAVE( 32 ) ) return 0;
+      i += 32UL;
+      unsigned w, r;
+      CU16( w );  if( !HAVE( w ) ) return 0;  i += w;
+      CU16( r );  if( !HAVE( r ) ) return 0;  i += r;
+      if( w > FD_TXN_CORE_ACCT_MAX - acct_cnt ) return 0;
+      if( r > FD_TXN_CORE_ACCT_MAX - acct_cnt ) return 0;
+      if( w + r < 1U ) return 0;
+      adtl += (unsigned long)w + r;
+    }
+  }
+  /* no "i==avail" here: :222 drops it when the size is asked for */
+  if( acct_cnt + adtl > FD_TXN_CORE_ACCT_MAX ) return 0;
+  if( !(max_acct < acct_cnt + adtl) ) return 0;
+#undef HAVE
+#undef CU16
+  return i;
+}
+
 #endif

@@ -25,6 +25,7 @@
 #include "../fd_precompile_core.h"
 #include "../fd_shred_core.h"
 #include "../fd_packet_core.h"
+#include "../fd_crds_core.h"
 #include "../fd_front_work.h"
 
 #include <hip/hip_runtime_api.h>
@@ -1701,6 +1702,148 @@ fd_ed25519_hip_packets_host( fd_ed25519_hip_engine_t * e, int proto, unsigned lo
   int err = front_begin( e, n, pkts && pkt_off && pkt_sz && out, 0UL, NULL, NULL, &st );
   if( err<=0 ) return err;
   return front_items_host( e, st, n, pkts, pkt_off, pkt_sz, NULL, proto, self_key, out, NULL );
+}
+
+/* ---- CRDS values of gossip pull responses and push messages (include/fd_ed25519_hip.h Part 2e) -- */
+
+_Static_assert( FD_ED25519_HIP_CRDS_OK==FD_CRDS_CORE_OK && FD_ED25519_HIP_CRDS_ERR_PARSE==FD_CRDS_CORE_ERR_PARSE &&
+                FD_ED25519_HIP_CRDS_UNSUPPORTED==FD_CRDS_CORE_UNSUPPORTED &&
+                FD_ED25519_HIP_CRDS_ERR_SIGNATURE==FD_CRDS_CORE_ERR_SIGNATURE &&
+                FD_ED25519_HIP_CRDS_OWN==FD_CRDS_CORE_OWN && FD_ED25519_HIP_CRDS_VAL_MAX==FD_CRDS_CORE_VAL_MAX &&
+                FD_ED25519_HIP_PACKET_MAX==FD_CRDS_CORE_MAX &&
+                FD_CRDS_CORE_HDR_SZ + FD_CRDS_CORE_VAL_MAX*FD_CRDS_CORE_VAL_MIN<=FD_CRDS_CORE_MAX &&
+                FD_CRDS_CORE_HDR_SZ + ( FD_CRDS_CORE_VAL_MAX+1UL )*FD_CRDS_CORE_VAL_MIN>FD_CRDS_CORE_MAX,
+                "public and core CRDS constants differ" );
+/* the plan's values are the core's, copied as bytes */
+_Static_assert( sizeof(fd_ed25519_hip_crds_val_t)==sizeof(fd_crds_core_val_t) &&
+                offsetof(fd_ed25519_hip_crds_val_t,disc   )==offsetof(fd_crds_core_val_t,disc   ) &&
+                offsetof(fd_ed25519_hip_crds_val_t,sig_off)==offsetof(fd_crds_core_val_t,sig_off) &&
+                offsetof(fd_ed25519_hip_crds_val_t,key_off)==offsetof(fd_crds_core_val_t,key_off) &&
+                offsetof(fd_ed25519_hip_crds_val_t,msg_off)==offsetof(fd_crds_core_val_t,msg_off) &&
+                offsetof(fd_ed25519_hip_crds_val_t,msg_sz )==offsetof(fd_crds_core_val_t,msg_sz ) &&
+                offsetof(fd_ed25519_hip_crds_val_t,pre    )==offsetof(fd_crds_core_val_t,pre    ),
+                "plan value layout" );
+
+/* count and plan: the walk the stage kernel runs, on the host (no GPU) */
+unsigned
+fd_ed25519_hip_crds_count( unsigned char const * pkt, unsigned long sz ) {
+  fd_crds_core_idx_t idx;
+  fd_crds_core_walk( pkt, sz, &idx );
+  return idx.cnt;
+}
+
+int
+fd_ed25519_hip_crds_plan( unsigned char const * pkt, unsigned long sz, unsigned char const self_key[ 32 ],
+                          fd_ed25519_hip_crds_val_t * vals, unsigned long cap, signed char * pkt_code ) {
+  if( !self_key ) return FD_ED25519_HIP_ERR_INVAL;
+  fd_crds_core_idx_t idx;
+  int code = fd_crds_core_walk( pkt, sz, &idx );
+  if( pkt_code ) *pkt_code = (signed char)code;
+  unsigned k = 0U;
+  for( ; vals && k<idx.cnt && k<cap; k++ ) {
+    fd_crds_core_val_t v = { 0 };
+    fd_crds_core_value( pkt, sz, &idx, k, self_key, &v );
+    memcpy( vals + k, &v, sizeof(v) );
+  }
+  return (int)k;
+}
+
+int
+fd_ed25519_hip_crds_dev( fd_ed25519_hip_engine_t * e, unsigned long n, unsigned char const * pkts,
+                         unsigned long const * pkt_off, unsigned int const * pkt_sz, unsigned long pkt_bytes,
+                         unsigned char const self_key[ 32 ], unsigned int const * val_first, unsigned long n_val,
+                         void * work, signed char * pkt_out, signed char * val_out, signed char * sig_out,
+                         unsigned char * hash_out, void * stream ) {
+  if( !self_key ) return FD_ED25519_HIP_ERR_INVAL;   /* of an empty batch too */
+  hipStream_t st;
+  int err = front_begin( e, n, pkts && pkt_off && pkt_sz && val_first && work && pkt_out && ( val_out || !n_val ) &&
+                               n_val<=n*FD_ED25519_HIP_CRDS_VAL_MAX && !( (uintptr_t)pkts & 3UL ) && !( (uintptr_t)hash_out & 3UL ),
+                         (uintptr_t)work, "crds work", stream, &st );
+  if( err<=0 ) return err;
+  front_work_t w;
+  err = front_work_fits( front_work_crds( work, n, n_val, &w ), FD_ED25519_HIP_CRDS_WORK_BYTES( n, n_val ), "crds" );
+  if( err ) return err;
+  fd_ed25519_crds_stage_params_t sp = { 0 };
+  sp.pkts = pkts; sp.pkt_off = (uint64_t const *)pkt_off; sp.pkt_sz = pkt_sz; sp.val_first = val_first;
+  sp.n = n; sp.n_val = n_val; sp.pkt_bytes = pkt_bytes;
+  memcpy( sp.self_key, self_key, 32UL );
+  sp.sigs = w.sigs; sp.pubs = w.pubs; sp.msg_off = w.msg_off; sp.msg_sz = w.msg_sz; sp.val_sz = w.val_sz; sp.pre = w.pre;
+  sp.status = w.status;
+  /* The stage fills the slots val_first reserves.  A val_first that is no prefix sum (it runs backwards, leaves n_val or
+     skips slots) leaves slots no lane fills, and the verify phases read every slot's message offset: empty messages at
+     offset 0 and BAD_RESERVATION for all, ahead of the stage (msg_off, msg_sz, val_sz and codes are adjacent). */
+  if( n_val ) {
+    HIPCHK( hipMemsetAsync( w.msg_off, 0, 17UL*n_val, st ), "crds slots memset" );
+    HIPCHK( hipMemsetAsync( w.pre, FD_ED25519_HIP_CRDS_BAD_RESERVATION & 0xFF, n_val, st ), "crds slots memset" );
+  }
+  err = fd_ed25519_hip_launch_crds_stage( &sp, st );
+  if( err ) return hip_fail( (hipError_t)err, "crds_stage launch" );
+  if( n_val ) {
+    err = verify_common( e, n_val, pkts, (unsigned long const *)w.msg_off, w.msg_sz, NULL, w.sigs, w.pubs,
+                         (signed char *)w.codes, st );
+    if( err ) return err;
+  }
+  fd_ed25519_crds_finish_params_t fp = { 0 };
+  fp.codes = w.codes; fp.pre = w.pre; fp.status = w.status; fp.n = n; fp.n_val = n_val;
+  fp.pkt_out = (int8_t *)pkt_out; fp.val_out = (int8_t *)val_out; fp.sig_out = (int8_t *)sig_out;
+  err = fd_ed25519_hip_launch_crds_finish( &fp, st );
+  if( err ) return hip_fail( (hipError_t)err, "crds_finish launch" );
+  if( hash_out ) {
+    fd_ed25519_crds_hash_params_t hp = { 0 };
+    hp.pkts = pkts; hp.msg_off = w.msg_off; hp.val_sz = w.val_sz; hp.n_val = n_val; hp.hash_out = hash_out;
+    err = fd_ed25519_hip_launch_crds_hash( &hp, st );
+    if( err ) return hip_fail( (hipError_t)err, "crds_hash launch" );
+  }
+  return FD_ED25519_HIP_OK;
+}
+
+/* pass by pass, as front_items_host; a pass counts the values from the packed copies, the ones the device will read.
+   in: off u64 [m], val_first u32 [m+1], sz u32 [m]; out: hashes [nv][32], value codes [nv], packet codes [m] */
+int
+fd_ed25519_hip_crds_host( fd_ed25519_hip_engine_t * e, unsigned long n, unsigned char const * pkts,
+                          unsigned long const * pkt_off, unsigned int const * pkt_sz, unsigned char const self_key[ 32 ],
+                          unsigned int * val_first_out, signed char * pkt_out, signed char * val_out,
+                          unsigned char * hash_out ) {
+  if( !self_key ) return FD_ED25519_HIP_ERR_INVAL;
+  if( e && val_first_out ) val_first_out[ 0 ] = 0U;
+  hipStream_t st;
+  int err = front_begin( e, n, pkts && pkt_off && pkt_sz && val_first_out && pkt_out && val_out, 0UL, NULL, NULL, &st );
+  if( err<=0 ) return err;
+  uint64_t total = 0UL;
+  for( uint64_t base=0UL; base<n; base+=FRONT_HOST_CHUNK ) {
+    uint64_t m = n-base<FRONT_HOST_CHUNK ? n-base : FRONT_HOST_CHUNK;
+    uint64_t first_at = 8UL*m, sz_at = 12UL*m + 4UL, in_bytes = 16UL*m + 4UL;
+    uint64_t out_max = 33UL*m*FD_ED25519_HIP_CRDS_VAL_MAX + m;
+    if( (err = front_room( e, m*FD_CRDS_CORE_MAX, in_bytes, out_max )) ) return err;
+    uint64_t * h_off   = (uint64_t *)e->h_fr_in;
+    uint32_t * h_first = (uint32_t *)( e->h_fr_in + first_at );
+    uint32_t * h_sz    = (uint32_t *)( e->h_fr_in + sz_at );
+    uint64_t pos = front_pack( e, m, pkts, pkt_off+base, pkt_sz+base, FD_CRDS_CORE_MAX, 0UL, h_off, h_sz );
+    uint64_t nv = 0UL;
+    for( uint64_t i=0UL; i<m; i++ ) {
+      h_first[i] = (uint32_t)nv;
+      val_first_out[ base+i ] = (unsigned int)( total + nv );
+      /* a packet of more than PACKET_MAX bytes travels as its size alone: the walk rejects the size unread */
+      nv += fd_ed25519_hip_crds_count( e->h_msgs + h_off[i], h_sz[i] );
+    }
+    h_first[m] = (uint32_t)nv;
+    val_first_out[ base+m ] = (unsigned int)( total + nv );
+    uint64_t hash_bytes = hash_out ? 32UL*nv : 0UL, out_bytes = hash_bytes + nv + m;
+    if( (err = grow_dev( &e->d_fr_work, &e->fr_work_cap, FD_ED25519_HIP_CRDS_WORK_BYTES( m, nv ) )) ) return err;
+    if( (err = front_upload( e, pos, in_bytes, st )) ) return err;
+    err = fd_ed25519_hip_crds_dev( e, m, e->d_msgs, (unsigned long const *)e->d_fr_in,
+                                   (unsigned int const *)( e->d_fr_in + sz_at ), pos, self_key,
+                                   (unsigned int const *)( e->d_fr_in + first_at ), nv, e->d_fr_work,
+                                   (signed char *)( e->d_fr_out + hash_bytes + nv ), (signed char *)( e->d_fr_out + hash_bytes ),
+                                   NULL, hash_out ? e->d_fr_out : NULL, st );
+    if( err ) return err;
+    if( (err = front_download( e, out_bytes, st )) ) return err;
+    if( hash_out ) memcpy( hash_out + 32UL*total, e->h_fr_out, hash_bytes );
+    memcpy( val_out + total, e->h_fr_out + hash_bytes, nv );
+    memcpy( pkt_out + base, e->h_fr_out + hash_bytes + nv, m );
+    total += nv;
+  }
+  return FD_ED25519_HIP_OK;
 }
 
 /* ---- drop-in API -------------------------------------------------------

@@ -200,6 +200,52 @@ def packet_plan(proto, pkt, self_key):
     if code == -22:   # FD_ED25519_HIP_ERR_INVAL: an unknown protocol
         raise ValueError("packet_plan: unknown protocol")
     return code, plan[0]
+
+
+# the CRDS values of gossip pull responses and push messages (include/fd_ed25519_hip.h Part 2e)
+CRDS_OK = 0
+CRDS_ERR_PARSE = -16
+CRDS_BAD_RESERVATION = -17
+CRDS_UNSUPPORTED = -18
+CRDS_ERR_SIGNATURE = -20
+CRDS_OWN = -21
+CRDS_VAL_MAX = 10
+# fd_ed25519_hip_crds_val_t
+CRDS_VAL_DTYPE = np.dtype([("disc", np.uint32), ("sig_off", np.uint16), ("key_off", np.uint16), ("msg_off", np.uint16),
+                           ("msg_sz", np.uint16), ("pre", np.int8)], align=True)
+_lib.fd_ed25519_hip_crds_count.argtypes = [ctypes.c_char_p, ctypes.c_ulong]
+_lib.fd_ed25519_hip_crds_count.restype = ctypes.c_uint
+_lib.fd_ed25519_hip_crds_plan.argtypes = [ctypes.c_char_p, ctypes.c_ulong, ctypes.c_char_p, ctypes.c_void_p, ctypes.c_ulong,
+                                          ctypes.POINTER(ctypes.c_byte)]
+_lib.fd_ed25519_hip_crds_dev.argtypes = [ctypes.c_void_p, ctypes.c_ulong] + [_u8p] * 3 + [ctypes.c_ulong, ctypes.c_char_p, _u8p,
+                                                                                         ctypes.c_ulong] + [_u8p] * 6
+_lib.fd_ed25519_hip_crds_host.argtypes = [ctypes.c_void_p, ctypes.c_ulong] + [_u8p] * 3 + [ctypes.c_char_p] + [_u8p] * 4
+
+
+def crds_work_bytes(n, n_val):
+    """FD_ED25519_HIP_CRDS_WORK_BYTES"""
+    return 114 * int(n_val) + int(n) + 16
+
+
+def crds_count(pkt):
+    """fd_ed25519_hip_crds_count: the values to reserve for one raw gossip
+    packet (host only)."""
+    pkt = bytes(pkt)
+    return _lib.fd_ed25519_hip_crds_count(pkt, len(pkt))
+
+
+def crds_plan(pkt, self_key):
+    """fd_ed25519_hip_crds_plan: (packet code, values as CRDS_VAL_DTYPE
+    records) of one raw gossip packet (host only): where each value's
+    signature, key and signed message lie, and pre = CRDS_OWN for a value
+    under self_key."""
+    pkt = bytes(pkt)
+    vals = np.zeros(CRDS_VAL_MAX, CRDS_VAL_DTYPE)
+    code = ctypes.c_byte(0)
+    n = _lib.fd_ed25519_hip_crds_plan(pkt, len(pkt), _self_key(self_key), vals.ctypes.data, len(vals), ctypes.byref(code))
+    return code.value, vals[:n]
+
+
 _lib.fd_ed25519_hip_last_error.restype = ctypes.c_char_p
 
 
@@ -398,6 +444,34 @@ class Engine:
         """Device-resident fd_ed25519_hip_precompile_dev: device addresses (ints); async."""
         _check(_lib.fd_ed25519_hip_precompile_dev(self._h, int(ntxn), d_payloads, d_off, d_sz, d_ent_first, int(n_ent),
                                                   d_work, d_txn_out, d_instr_out, d_ent_out, stream))
+
+    def crds_host(self, pkts, self_key, want_hashes=False):
+        """The CRDS values of raw gossip pull responses and push messages
+        (fd_ed25519_hip_crds_host) under the validator's own identity
+        self_key -> (int8 code per packet, uint32 val_first [n + 1], int8 code
+        per value, the values of packet i at val_first[i]..val_first[i + 1])
+        and, with want_hashes, uint8 [n_val, 32] value hashes; synchronous."""
+        from .tile import pack_payloads
+        n = len(pkts)
+        self_key = _self_key(self_key)
+        pkt_codes, first = np.zeros(n, np.int8), np.zeros(n + 1, np.uint32)
+        vals = np.zeros(max(1, sum(crds_count(p) for p in pkts)), np.int8)
+        hashes = np.zeros((len(vals), 32), np.uint8) if want_hashes else None
+        if n:
+            buf, off, sz = pack_payloads(pkts)
+            _check(_lib.fd_ed25519_hip_crds_host(self._h, n, _ptr(buf), _ptr(off), _ptr(sz), self_key, _ptr(first),
+                                                 _ptr(pkt_codes), _ptr(vals), _ptr(hashes)))
+        n_val = int(first[n])
+        out = (pkt_codes, first, vals[:n_val])
+        return out + (hashes[:n_val],) if want_hashes else out
+
+    def crds_dev(self, n, d_pkts, d_off, d_sz, pkt_bytes, self_key, d_val_first, n_val, d_work, d_pkt_out, d_val_out,
+                 d_sig_out=None, d_hash_out=None, stream=None):
+        """Device-resident fd_ed25519_hip_crds_dev: device addresses (ints),
+        self_key 32 host bytes; async."""
+        _check(_lib.fd_ed25519_hip_crds_dev(self._h, int(n), d_pkts, d_off, d_sz, int(pkt_bytes), _self_key(self_key),
+                                            d_val_first, int(n_val), d_work, d_pkt_out, d_val_out, d_sig_out, d_hash_out,
+                                            stream))
 
 
     # ---- batched signing / synthetic workloads -------------------------

@@ -211,14 +211,15 @@ typedef struct fd_ed25519_hip_engine fd_ed25519_hip_engine_t;
    the drop-in's and the pipe's host-scalar, host-decode and split-waves
    setters, latency_set_cpus; 11: Part 2b, the Ed25519 precompile
    instructions of raw transactions; 12: Part 2c, the leader signatures of
-   Merkle shreds; 13: Part 2d, signed gossip and repair control packets).
+   Merkle shreds; 13: Part 2d, signed gossip and repair control packets; 14:
+   Part 2e, the CRDS values of gossip pull responses and push messages).
    A consumer checks
    the library it loaded against the header it was built with:
    fd_ed25519_hip_abi_check( FD_ED25519_HIP_ABI_VERSION,
    sizeof(fd_ed25519_hip_slot_t), sizeof(fd_ed25519_hip_info_t),
    sizeof(fd_ed25519_hip_vservice_stats_t) ) returns 0 when they agree,
    FD_ED25519_HIP_ERR_INVAL (with fd_ed25519_hip_last_error) when not. */
-#define FD_ED25519_HIP_ABI_VERSION (13U)
+#define FD_ED25519_HIP_ABI_VERSION (14U)
 
 unsigned
 fd_ed25519_hip_abi_version( void );
@@ -679,10 +680,9 @@ fd_ed25519_hip_shreds_host( fd_ed25519_hip_engine_t * engine,
    bytes left over, gets PACKET_ERR_PARSE -- and so does one of fewer than 4
    or more than FD_ED25519_HIP_PACKET_MAX bytes (no larger UDP payload
    reaches the reference's handlers).  A gossip pull request, pull response
-   or push message gets PACKET_UNSUPPORTED without a further look: their
-   CRDS values need the bincode walk of every fd_crds_data variant and a
-   re-encode, and stay on the caller's CPU path; so do, where they decode,
-   a repair pong (its signed message is a hash of the caller's own ping
+   or push message gets PACKET_UNSUPPORTED without a further look: the
+   CRDS values of the last two are Part 2e's, and a pull request stays on
+   the caller's CPU path; so do, where they decode, a repair pong (its signed message is a hash of the caller's own ping
    token), ancestor_hashes and the seven legacy request kinds.  A prune
    message whose destination, or a repair request whose recipient, is not
    self_key gets PACKET_NOT_FOR_SELF: the reference drops it unverified.  A
@@ -783,6 +783,183 @@ fd_ed25519_hip_packets_host( fd_ed25519_hip_engine_t * engine,
                              unsigned int const *      pkt_sz,
                              unsigned char const       self_key[ 32 ],
                              signed char *             out );
+
+/* ---- Part 2e: the CRDS values of gossip pull responses and push messages -- */
+
+/* Most of the signed traffic of a validator's gossip port is CRDS values: a
+   pull response or a push message carries several, each with a signature of
+   its own, and the reference verifies them one fd_ed25519_verify call at a
+   time (fd_gossip_recv_crds_value, src/flamenco/gossip/fd_gossip.c:1020-1091,
+   called for every value at :1420-1430).  The entry points below take a batch
+   of raw gossip packets with the validator's own identity and do the bincode
+   walk of every fd_crds_data variant, the choice of each value's key, the
+   gather and the verification on the device.  The reservation model is Part
+   2b's: the caller reserves each packet's value slots from crds_count.
+
+   Per packet: one the reference's fd_gossip_msg_decode rejects, or decodes
+   with bytes left over, gets CRDS_ERR_PARSE and none of its values a verdict
+   (fd_gossip_recv_packet drops the packet whole, fd_gossip.c:1868-1877) --
+   and so does one of fewer than 4 or more than FD_ED25519_HIP_PACKET_MAX
+   bytes.  A pull request, prune, ping or pong gets CRDS_UNSUPPORTED unread:
+   they are Part 2d's, or (the pull request, in which the reference verifies
+   nothing) the caller's.  A pull response or push message that decodes gets
+   0.
+
+   Per value of a decoded packet: the key is the variant's own id / from for
+   data discriminants 0..10 and the message's outer pubkey for 11
+   (contact_info_v2: the reference's switch has no case for it,
+   fd_gossip.c:1023-1071).  A value whose key is self_key gets CRDS_OWN: the
+   reference drops it unverified (:1072).  The reference then signs over a
+   re-encode of the decoded value (:1075-1082), not over the received bytes.
+   For data discriminants 0..10 the two are equal for every encoding its
+   decoders accept, and the signed message -- the value's data, discriminant
+   and fields -- is read in place.  For contact_info_v2 they never are: the
+   reference decodes version_v3's fields and the socket entries' offsets as
+   compact-u16 and encodes them as plain u16 (fd_types.c:20626-20636 against
+   :20703-20713, :21109 against :21162), so it verifies bytes no peer signed.
+   Such a value gets CRDS_UNSUPPORTED and stays with the caller: this library
+   gives no verdict over bytes the reference would not have hashed.  A value
+   that fd_ed25519_verify does not accept -- whatever its code, so both code
+   flavours agree -- gets CRDS_ERR_SIGNATURE, every other one 0.  All codes
+   are this library's. */
+#define FD_ED25519_HIP_CRDS_OK              (  0)
+#define FD_ED25519_HIP_CRDS_ERR_PARSE       (-16)  /* the reference's decode fails or leaves bytes over */
+/* the caller reserved another number of values for the packet than the
+   device's walk of it found (crds_dev) */
+#define FD_ED25519_HIP_CRDS_BAD_RESERVATION (-17)
+#define FD_ED25519_HIP_CRDS_UNSUPPORTED     (-18)  /* a packet: no pull response or push message; a value: contact_info_v2 */
+#define FD_ED25519_HIP_CRDS_ERR_SIGNATURE   (-20)
+#define FD_ED25519_HIP_CRDS_OWN             (-21)  /* under the own identity: the reference drops it unverified */
+
+/* The most values one packet can decode to.  The smallest encodable value
+   is a version_v1 without commit: signature 64, data discriminant 4, from
+   32, wallclock 8, three u16, option tag 1 = 115 bytes (every other variant
+   is longer: slot_hashes 116, epoch_slots 117, version_v2 119,
+   node_instance 124, contact_info_v2 126, duplicate_shred 133, lowest_slot
+   141, incremental_snapshot_hashes 156, contact_info_v1 210, a vote more);
+   the values follow 44 bytes (message discriminant 4, pubkey 32, crds_len 8)
+   inside a 1232-byte packet: (1232-44)/115. */
+#define FD_ED25519_HIP_CRDS_VAL_MAX (10UL)
+
+/* The values to reserve for one packet: crds_len for a pull response or push
+   message that decodes, 0 for any other packet, 0..FD_ED25519_HIP_CRDS_VAL_MAX.
+   Host only. */
+unsigned
+fd_ed25519_hip_crds_count( unsigned char const * pkt, unsigned long sz );
+
+/* One value of a packet's staging plan: offsets relative to the packet.
+   The signature is pkt[sig_off..+64), the key pkt[key_off..+32), the signed
+   message pkt[msg_off..+msg_sz), which starts with disc, the data
+   discriminant; the value's own bytes, the ones hash_out hashes, are
+   pkt[sig_off..msg_off+msg_sz).  pre is 0, CRDS_OWN or CRDS_UNSUPPORTED (the
+   offsets are filled all the same; for CRDS_UNSUPPORTED they name the
+   received bytes, which are not what the reference verifies). */
+typedef struct {
+  unsigned int   disc;
+  unsigned short sig_off;
+  unsigned short key_off;
+  unsigned short msg_off;
+  unsigned short msg_sz;
+  signed char    pre;
+} fd_ed25519_hip_crds_val_t;
+
+/* The staging plan of one packet, host only (no GPU): what the device's
+   stage kernel lays out, from the same source.  Writes the first cap of the
+   packet's crds_count values (vals may be NULL with cap 0) and returns how
+   many it wrote; *pkt_code (optional) receives the packet's code.  A NULL
+   self_key gives FD_ED25519_HIP_ERR_INVAL.  Reads pkt[0..sz) only. */
+int
+fd_ed25519_hip_crds_plan( unsigned char const *       pkt,
+                          unsigned long               sz,
+                          unsigned char const         self_key[ 32 ],
+                          fd_ed25519_hip_crds_val_t * vals,
+                          unsigned long               cap,
+                          signed char *               pkt_code );
+
+/* Device workspace of crds_dev for n packets and n_val values: per value
+   the gathered signature (64) and key (32), the message's offset (8) and
+   size (4), the size of the value's data (4), the verify code and the
+   stage's code; per packet its code.  No message area: messages are read in
+   place. */
+#define FD_ED25519_HIP_CRDS_WORK_BYTES( n, n_val ) \
+  ( 114UL*(unsigned long)(n_val) + (unsigned long)(n) + 16UL )
+
+/* Device-resident batch: every pointer but the engine and self_key is a
+   device pointer.  Packet i is pkts[pkt_off[i] .. pkt_off[i] + pkt_sz[i])
+   and may start at any byte; the caller reserved the values [val_first[i],
+   val_first[i+1]) for it from fd_ed25519_hip_crds_count (val_first[0]==0,
+   val_first[n]==n_val, n_val given by value: the call reads nothing back).
+   A packet that decodes but whose reservation differs from what the
+   device's walk of it finds gets CRDS_BAD_RESERVATION; nothing is written
+   outside its reservation and no other packet's result changes.  A
+   val_first that is no such prefix sum is survived: a packet whose range
+   runs backwards or leaves [0, n_val) fills no slot, and a slot no packet
+   fills gets CRDS_BAD_RESERVATION in val_out.
+   pkt_off[i] + pkt_sz[i] <= pkt_bytes: a packet that leaves that range gets
+   CRDS_ERR_PARSE and is not read.
+
+   pkt_out[i] receives the packet's code.  val_out per value: 0,
+   CRDS_ERR_SIGNATURE, CRDS_OWN or CRDS_UNSUPPORTED; for the slots of a packet
+   whose code is not 0, that code.  sig_out (optional): fd_ed25519_verify's own code for
+   every verified value (in the engine's code flavour) and 0 for any other.
+   hash_out (optional, 32 bytes a value, 4-byte aligned): the SHA-256 of the
+   value's own bytes, signature through end of data -- the key of the
+   reference's value table (fd_gossip.c:1093-1105; the lookup stays with the
+   caller) -- for every value of a packet whose code is 0, CRDS_OWN ones
+   included, but for contact_info_v2 (the reference hashes a re-encode there
+   too), and zero for the others; the pass that computes it runs only when it
+   is asked for.  work: 16-byte aligned,
+   FD_ED25519_HIP_CRDS_WORK_BYTES( n, n_val ) bytes.
+
+   Messages are read in place, so the rules for the packet buffer are
+   precompile_dev's: it starts 4-byte aligned and stays readable at least 16
+   bytes past pkt_bytes, and packets do not overlap.
+
+   Asynchronous on `stream` (NULL: the engine's) like
+   fd_ed25519_hip_verify_dev, whose phases it runs over the n_val slots
+   (chunked by the engine's max_chunk; none when n_val is 0): it allocates
+   nothing beyond what that call may (its second lane on an engine's first
+   multi-chunk call) and does not synchronise.  A NULL self_key gives
+   FD_ED25519_HIP_ERR_INVAL; n==0 is a no-op. */
+int
+fd_ed25519_hip_crds_dev( fd_ed25519_hip_engine_t * engine,
+                         unsigned long             n,
+                         unsigned char const *     pkts,
+                         unsigned long const *     pkt_off,
+                         unsigned int const *      pkt_sz,
+                         unsigned long             pkt_bytes,
+                         unsigned char const       self_key[ 32 ],
+                         unsigned int const *      val_first,
+                         unsigned long             n_val,
+                         void *                    work,
+                         signed char *             pkt_out,
+                         signed char *             val_out,
+                         signed char *             sig_out,
+                         unsigned char *           hash_out,
+                         void *                    stream );
+
+/* Host-buffer batch, synchronous: counts every packet while packing them
+   back to back into pinned staging memory (in as many passes as the engine's
+   staging needs, so any n fits; here packets may overlap or repeat in the
+   caller's buffer), copies, runs crds_dev on a workspace the engine owns and
+   copies the results back.  val_first_out[0..n] receives the prefix sums of
+   the counts it used: the values of packet i are val_out[val_first_out[i] ..
+   val_first_out[i+1]), and hash_out (optional) is indexed the same way.  The
+   caller sizes val_out (and hash_out) for the sum of
+   fd_ed25519_hip_crds_count over the batch, at most
+   n*FD_ED25519_HIP_CRDS_VAL_MAX.  A packet of more than
+   FD_ED25519_HIP_PACKET_MAX bytes travels as its size alone. */
+int
+fd_ed25519_hip_crds_host( fd_ed25519_hip_engine_t * engine,
+                          unsigned long             n,
+                          unsigned char const *     pkts,
+                          unsigned long const *     pkt_off,
+                          unsigned int const *      pkt_sz,
+                          unsigned char const       self_key[ 32 ],
+                          unsigned int *            val_first_out,
+                          signed char *             pkt_out,
+                          signed char *             val_out,
+                          unsigned char *           hash_out );
 
 /* ---- Part 3: batched signing and the synthetic workload generator ------ */
 
