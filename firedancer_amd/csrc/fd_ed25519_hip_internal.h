@@ -569,6 +569,46 @@ int fd_ed25519_hip_launch_crds_stage( fd_ed25519_crds_stage_params_t const * p, 
 int fd_ed25519_hip_launch_crds_finish( fd_ed25519_crds_finish_params_t const * p, void * stream );
 int fd_ed25519_hip_launch_crds_hash( fd_ed25519_crds_hash_params_t const * p, void * stream );
 
+/* ---- sealing a leader's FEC sets (fd_ed25519_fec.hip) ---- */
+
+/* tree: workgroup k applies fd_fec_core.h's rules to the shreds
+   [set_first[k], set_first[k+1]), builds their Merkle tree, writes every
+   shred's proof and leaves the root as message k of the sign kernel -- an
+   empty message and a zero root for a set with a code, whose shreds it does
+   not write */
+typedef struct {
+  uint8_t *        shreds;     /* shred bytes, readable 16 B past each      */
+  uint64_t const * shred_off;  /* [n]                                       */
+  uint32_t const * shred_sz;   /* [n]                                       */
+  uint64_t         n;
+  uint32_t const * set_first;  /* [n_set+1]                                 */
+  uint64_t         n_set;
+  uint8_t *        roots;      /* [n_set][32] out, 16-B aligned: the messages */
+  uint64_t *       msg_off;    /* [n_set] out: 32 k, into roots             */
+  uint32_t *       msg_sz;     /* [n_set] out: 32, or 0                     */
+  uint32_t *       set_of;     /* [n] preset to ~0; out: k for a sealed set's shreds */
+  int8_t *         set_out;    /* [n_set] out: 0, ERR_PARSE, UNSUPPORTED, ERR_SET */
+  uint8_t *        roots_out;  /* [n_set][32] 16-B aligned, or NULL         */
+} fd_ed25519_fec_tree_params_t;
+
+/* scatter: lane i < n copies signature set_of[i] into shred i; lane k <
+   n_set the caller's copy of signature k */
+typedef struct {
+  uint8_t *        shreds;
+  uint64_t const * shred_off;
+  uint64_t         n;
+  uint64_t         n_set;
+  uint32_t const * set_of;
+  uint8_t const *  sigs;       /* [n_set][64] the sign kernel's             */
+  int8_t const *   set_out;
+  uint8_t *        sigs_out;   /* [n_set][64] 16-B aligned, or NULL         */
+} fd_ed25519_fec_scatter_params_t;
+
+int fd_ed25519_hip_launch_fec_tree( fd_ed25519_fec_tree_params_t const * p, void * stream );
+int fd_ed25519_hip_launch_fec_scatter( fd_ed25519_fec_scatter_params_t const * p, void * stream );
+/* the tree kernel's workgroup size as built (tools/fec_bench.py reports it) */
+unsigned fd_ed25519_hip_private_fec_tree_block( void );
+
 /* ---- generator (fd_ed25519_gen.hip) ---- */
 
 typedef struct {

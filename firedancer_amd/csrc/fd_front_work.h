@@ -3,7 +3,7 @@
    out of the caller's 16-byte-aligned buffer.  Plain C11, host only, nothing
    but pointer arithmetic: the engine (host/fd_ed25519_hip_engine.c) takes
    its kernels' arrays from here, and tests/front_work_main.c (the CRDS
-   front's: tests/crds_work_main.c) holds every layout to the public
+   front's: tests/crds_work_main.c, the FEC seal's: tests/fec_work_main.c) holds every layout to the public
    FD_ED25519_HIP_*_WORK_BYTES macro a caller sizes the buffer with.  A layout has no padding: the elements only get smaller, so
    every array is aligned to its element at any count. */
 #ifndef FD_FRONT_WORK_H
@@ -33,6 +33,8 @@ typedef struct {      /* in the buffer's order; [n] slots */
   uint8_t *  hdr_instr;
   uint8_t *  hdr_pos;
   uint32_t * val_sz;                          /* the CRDS front's: [n_val], the size of a value's data */
+  uint8_t *  roots;                           /* the FEC seal's: [n_set][32], the sign kernel's messages */
+  uint32_t * set_of;                          /* ... and [n], the set that sealed a shred */
 } front_work_t;
 
 /* what every layout begins with */
@@ -87,6 +89,22 @@ front_work_crds( void * work, uint64_t n, uint64_t n_val, front_work_t * w ) {
   w->codes   = (int8_t *)  front_carve( &c, n_val, 1UL );
   w->pre     = (int8_t *)  front_carve( &c, n_val, 1UL );
   w->status  = (int8_t *)  front_carve( &c, n,     1UL );
+  return (uint64_t)( c - (uint8_t *)work );
+}
+
+/* The FEC seal (fd_ed25519_hip_fec_seal_dev) has no verify phases: [n_set]
+   slots of the sign kernel -- signature, public key, the root as the
+   message, its offset and size -- and the set of each of the n shreds. */
+static inline uint64_t
+front_work_fec( void * work, uint64_t n, uint64_t n_set, front_work_t * w ) {
+  uint8_t * c = (uint8_t *)work;
+  *w = (front_work_t){ 0 };
+  w->sigs    = (uint8_t *) front_carve( &c, n_set, 64UL );
+  w->pubs    = (uint8_t *) front_carve( &c, n_set, 32UL );
+  w->roots   = (uint8_t *) front_carve( &c, n_set, 32UL );
+  w->msg_off = (uint64_t *)front_carve( &c, n_set, 8UL );
+  w->msg_sz  = (uint32_t *)front_carve( &c, n_set, 4UL );
+  w->set_of  = (uint32_t *)front_carve( &c, n,     4UL );
   return (uint64_t)( c - (uint8_t *)work );
 }
 

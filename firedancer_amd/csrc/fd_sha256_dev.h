@@ -215,6 +215,32 @@ FD_DEV void sha256_node(uint32_t (&h)[8], const sha256_node_raw& r, bool right) 
   sha256_block(h, w);
 }
 
+/* h = SHA-256( node prefix || left[0..20) || right[0..20) ) with both
+   children given as big-endian words (registers, or LDS rows of a tree held
+   by a workgroup: fd_ed25519_fec.hip); the two blocks of sha256_node */
+FD_DEV void sha256_node_pair(uint32_t (&h)[8], const uint32_t (&left)[5], const uint32_t (&right)[5]) {
+  uint32_t x[10];
+#pragma unroll
+  for (int i = 0; i < 5; i++) {
+    x[i] = left[i];
+    x[5 + i] = right[i];
+  }
+  uint32_t w[16];
+  w[0] = SHA256_PRE_W0(1); w[1] = SHA256_PRE_W1; w[2] = SHA256_PRE_W2; w[3] = SHA256_PRE_W3; w[4] = SHA256_PRE_W4;
+  w[5] = SHA256_NODE_W5;
+  w[6] = SHA256_NODE_W6 | (x[0] >> 16);
+#pragma unroll
+  for (int i = 0; i < 9; i++) w[7 + i] = __builtin_amdgcn_alignbit(x[i], x[i + 1], 16);
+  const uint32_t last = (x[9] << 16) | 0x8000u;   /* stream bytes 64, 65 and the padding's 0x80 */
+  sha256_init(h);
+  sha256_block(h, w);
+  w[0] = last;
+#pragma unroll
+  for (int t = 1; t < 15; t++) w[t] = 0u;
+  w[15] = (FD_SHRED_CORE_PREFIX_SZ + 2u * FD_SHRED_CORE_NODE_SZ) << 3;
+  sha256_block(h, w);
+}
+
 /* Rules 4-5 of fd_shred_core.h for a shred fd_shred_core_judge passed: the
    root as eight big-endian words.  The next layer's sibling is loaded
    before the current layer is hashed. */

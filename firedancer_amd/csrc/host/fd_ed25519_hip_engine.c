@@ -26,6 +26,7 @@
 #include "../fd_shred_core.h"
 #include "../fd_packet_core.h"
 #include "../fd_crds_core.h"
+#include "../fd_fec_core.h"
 #include "../fd_front_work.h"
 
 #include <hip/hip_runtime_api.h>
@@ -1842,6 +1843,135 @@ fd_ed25519_hip_crds_host( fd_ed25519_hip_engine_t * e, unsigned long n, unsigned
     memcpy( val_out + total, e->h_fr_out + hash_bytes, nv );
     memcpy( pkt_out + base, e->h_fr_out + hash_bytes + nv, m );
     total += nv;
+  }
+  return FD_ED25519_HIP_OK;
+}
+
+/* ---- sealing a leader's FEC sets (include/fd_ed25519_hip.h Part 2f) ------ */
+
+_Static_assert( FD_ED25519_HIP_FEC_OK==FD_FEC_CORE_OK && FD_ED25519_HIP_FEC_ERR_PARSE==FD_FEC_CORE_ERR_PARSE &&
+                FD_ED25519_HIP_FEC_UNSUPPORTED==FD_FEC_CORE_UNSUPPORTED && FD_ED25519_HIP_FEC_ERR_SET==FD_FEC_CORE_ERR_SET &&
+                FD_ED25519_HIP_FEC_ERR_SET==FD_ED25519_HIP_SHRED_ERR_HEADER &&
+                FD_ED25519_HIP_FEC_SET_MAX==FD_FEC_CORE_CNT_MAX,
+                "public and core FEC constants differ" );
+
+/* the rules and the tree the tree kernel runs, on the host (no GPU) */
+int
+fd_ed25519_hip_fec_root( unsigned char const * shreds, unsigned long const * shred_off, unsigned int const * shred_sz,
+                         unsigned long cnt, unsigned char * root, unsigned char * proofs ) {
+  if( !root ) return FD_ED25519_HIP_ERR_INVAL;
+  return fd_fec_core_root( shreds, shred_off, shred_sz, cnt, root, proofs );
+}
+
+int
+fd_ed25519_hip_fec_seal_dev( fd_ed25519_hip_engine_t * e, unsigned long n, unsigned char * shreds,
+                             unsigned long const * shred_off, unsigned int const * shred_sz, unsigned long n_set,
+                             unsigned int const * set_first, unsigned char const * privs, void * work,
+                             signed char * set_out, unsigned char * roots, unsigned char * sigs, void * stream ) {
+  hipStream_t st;
+  /* the batch is its sets: none is a no-op whatever n is; a signature copy needs the keys */
+  int err = front_begin( e, n_set, set_first && work && set_out && ( !n || ( shreds && shred_off && shred_sz ) ) &&
+                                   n<=UINT32_MAX && n_set<=INT32_MAX && ( privs || !sigs ),
+                         (uintptr_t)work | (uintptr_t)privs | (uintptr_t)roots | (uintptr_t)sigs | (uintptr_t)shreds,
+                         "shreds/privs/work/roots/sigs", stream, &st );
+  if( err<=0 ) return err;
+  front_work_t w;
+  if( (err = front_work_fits( front_work_fec( work, n, n_set, &w ), FD_ED25519_HIP_FEC_WORK_BYTES( n, n_set ), "fec" )) ) return err;
+  /* no set has sealed a shred yet; the scatter reads every shred's entry */
+  if( n ) HIPCHK( hipMemsetAsync( w.set_of, 0xFF, 4UL*n, st ), "fec set_of memset" );
+  fd_ed25519_fec_tree_params_t tp = { 0 };
+  tp.shreds = shreds; tp.shred_off = (uint64_t const *)shred_off; tp.shred_sz = shred_sz; tp.n = n;
+  tp.set_first = set_first; tp.n_set = n_set;
+  tp.roots = w.roots; tp.msg_off = w.msg_off; tp.msg_sz = w.msg_sz; tp.set_of = w.set_of;
+  tp.set_out = (int8_t *)set_out; tp.roots_out = roots;
+  err = fd_ed25519_hip_launch_fec_tree( &tp, st );
+  if( err ) return hip_fail( (hipError_t)err, "fec_tree launch" );
+  if( !privs ) return FD_ED25519_HIP_OK;   /* the keyguard split: the caller signs the roots elsewhere */
+  fd_ed25519_sign_params_t gp = { 0 };
+  gp.msgs = w.roots; gp.msg_off = w.msg_off; gp.msg_sz = w.msg_sz; gp.privs = privs;
+  gp.sigs = w.sigs; gp.pubs = w.pubs; gp.n = n_set; gp.btab = e->d_btab;
+  err = fd_ed25519_hip_launch_sign( &gp, st );
+  if( err ) return hip_fail( (hipError_t)err, "fec sign launch" );
+  fd_ed25519_fec_scatter_params_t cp = { 0 };
+  cp.shreds = shreds; cp.shred_off = (uint64_t const *)shred_off; cp.n = n; cp.n_set = n_set;
+  cp.set_of = w.set_of; cp.sigs = w.sigs; cp.set_out = (int8_t const *)set_out; cp.sigs_out = sigs;
+  err = fd_ed25519_hip_launch_fec_scatter( &cp, st );
+  if( err ) return hip_fail( (hipError_t)err, "fec_scatter launch" );
+  return FD_ED25519_HIP_OK;
+}
+
+/* Pass by pass, whole sets at a time: up to FRONT_HOST_CHUNK shreds and as
+   many sets.  A set whose range runs backwards, leaves [0, n) or holds more
+   than FEC_SET_MAX shreds travels as an empty set, which is the same code.
+   No rule reads and no kernel writes a byte at or past FD_SHRED_MAX_SZ, so a
+   longer shred travels as its head and its true size.
+   in: privs [ms][32], off u64 [m], set_first u32 [ms+1], sz u32 [m];
+   out: roots [ms][32], sigs [ms][64], codes [ms].  Of a sealed set's shreds
+   the signature (with privs) and the proof are copied back, nothing else. */
+int
+fd_ed25519_hip_fec_seal_host( fd_ed25519_hip_engine_t * e, unsigned long n, unsigned char * shreds,
+                              unsigned long const * shred_off, unsigned int const * shred_sz, unsigned long n_set,
+                              unsigned int const * set_first, unsigned char const * privs, signed char * set_out,
+                              unsigned char * roots, unsigned char * sigs ) {
+  hipStream_t st;
+  int err = front_begin( e, n_set, set_first && set_out && ( !n || ( shreds && shred_off && shred_sz ) ) && n<=UINT32_MAX &&
+                                   ( privs || !sigs ), 0UL, NULL, NULL, &st );
+  if( err<=0 ) return err;
+  for( uint64_t k0=0UL; k0<n_set; ) {
+    uint64_t k1 = k0, m = 0UL;
+    for( ; k1<n_set && k1-k0<FRONT_HOST_CHUNK; k1++ ) {
+      uint64_t first = set_first[k1], last = set_first[k1+1UL];
+      uint64_t cnt = ( first<=last && last<=n && last-first<=FD_FEC_CORE_CNT_MAX ) ? last-first : 0UL;
+      if( m+cnt>FRONT_HOST_CHUNK ) break;
+      m += cnt;
+    }
+    uint64_t ms = k1-k0, priv_bytes = privs ? 32UL*ms : 0UL;
+    uint64_t off_at = priv_bytes, first_at = off_at + 8UL*m, sz_at = first_at + 4UL*( ms+1UL ), in_bytes = sz_at + 4UL*m;
+    uint64_t sigs_at = 32UL*ms, codes_at = 96UL*ms, out_bytes = 97UL*ms;
+    if( (err = front_room( e, m*FD_SHRED_CORE_MAX_SZ, in_bytes, out_bytes )) ) return err;
+    uint64_t * h_off   = (uint64_t *)( e->h_fr_in + off_at );
+    uint32_t * h_first = (uint32_t *)( e->h_fr_in + first_at );
+    uint32_t * h_sz    = (uint32_t *)( e->h_fr_in + sz_at );
+    if( privs ) memcpy( e->h_fr_in, privs + 32UL*k0, priv_bytes );
+    uint64_t pos = 0UL, i = 0UL;
+    for( uint64_t k=k0; k<k1; k++ ) {
+      uint64_t first = set_first[k], last = set_first[k+1UL];
+      uint64_t cnt = ( first<=last && last<=n && last-first<=FD_FEC_CORE_CNT_MAX ) ? last-first : 0UL;
+      h_first[ k-k0 ] = (uint32_t)i;
+      for( uint64_t j=first; j<first+cnt; j++, i++ ) {
+        uint64_t cp = shred_sz[j]<=FD_SHRED_CORE_MAX_SZ ? shred_sz[j] : FD_SHRED_CORE_MAX_SZ;
+        if( cp ) memcpy( e->h_msgs + pos, shreds + shred_off[j], cp );
+        h_off[i] = pos;
+        h_sz [i] = shred_sz[j];
+        pos += cp;
+      }
+    }
+    h_first[ ms ] = (uint32_t)i;
+    if( (err = grow_dev( &e->d_fr_work, &e->fr_work_cap, FD_ED25519_HIP_FEC_WORK_BYTES( m, ms ) )) ) return err;
+    if( (err = front_upload( e, pos, in_bytes, st )) ) return err;
+    err = fd_ed25519_hip_fec_seal_dev( e, m, e->d_msgs, (unsigned long const *)( e->d_fr_in + off_at ),
+                                       (unsigned int const *)( e->d_fr_in + sz_at ), ms,
+                                       (unsigned int const *)( e->d_fr_in + first_at ), privs ? e->d_fr_in : NULL,
+                                       e->d_fr_work, (signed char *)( e->d_fr_out + codes_at ), e->d_fr_out,
+                                       privs ? e->d_fr_out + sigs_at : NULL, st );
+    if( err ) return err;
+    if( pos ) HIPCHK( hipMemcpyAsync( e->h_msgs, e->d_msgs, pos, hipMemcpyDeviceToHost, st ), "D2H sealed shreds" );
+    if( (err = front_download( e, out_bytes, st )) ) return err;
+    memcpy( set_out + k0, e->h_fr_out + codes_at, ms );
+    if( roots ) memcpy( roots + 32UL*k0, e->h_fr_out, 32UL*ms );
+    if( sigs )  memcpy( sigs  + 64UL*k0, e->h_fr_out + sigs_at, 64UL*ms );
+    for( uint64_t k=k0; k<k1; k++ ) {
+      if( set_out[k] ) continue;                      /* rule 6 */
+      uint64_t first = set_first[k], cnt = set_first[k+1UL]-first, depth = fd_fec_core_depth( (unsigned)cnt );
+      for( uint64_t j=0UL; j<cnt; j++ ) {
+        unsigned char *       dst = shreds + shred_off[ first+j ];
+        unsigned char const * src = e->h_msgs + h_off[ h_first[ k-k0 ]+j ];
+        uint64_t proof_at = ( ( src[ 0x40 ] & 0xf0 )==0x80 ? FD_SHRED_CORE_MIN_SZ : FD_SHRED_CORE_MAX_SZ ) - 20UL*depth;
+        if( privs ) memcpy( dst, src, 64UL );
+        memcpy( dst + proof_at, src + proof_at, 20UL*depth );
+      }
+    }
+    k0 = k1;
   }
   return FD_ED25519_HIP_OK;
 }

@@ -159,6 +159,46 @@ def shred_root(shred):
     return code, (root.raw if code == 0 else None)
 
 
+# sealing a leader's FEC sets (include/fd_ed25519_hip.h Part 2f)
+FEC_OK = 0
+FEC_ERR_PARSE = -16
+FEC_UNSUPPORTED = -18
+FEC_ERR_SET = -19
+FEC_SET_MAX = 134
+_lib.fd_ed25519_hip_fec_root.argtypes = [_u8p, _u8p, _u8p, ctypes.c_ulong, ctypes.c_char_p, _u8p]
+_lib.fd_ed25519_hip_fec_seal_dev.argtypes = [ctypes.c_void_p, ctypes.c_ulong] + [_u8p] * 3 + [ctypes.c_ulong] + [_u8p] * 7
+_lib.fd_ed25519_hip_fec_seal_host.argtypes = [ctypes.c_void_p, ctypes.c_ulong] + [_u8p] * 3 + [ctypes.c_ulong] + [_u8p] * 5
+
+
+def fec_work_bytes(n, n_set):
+    """FD_ED25519_HIP_FEC_WORK_BYTES"""
+    return 140 * int(n_set) + 4 * int(n) + 16
+
+
+def fec_depth(cnt):
+    """proof nodes of a leaf in a set of cnt shreds (fd_bmtree_depth( cnt ) - 1)"""
+    return (int(cnt) - 1).bit_length()
+
+
+def fec_root(shreds):
+    """fd_ed25519_hip_fec_root: (code, 32-byte root, the 20 depth proof bytes
+    of every shred) of one FEC set given as its raw shreds in tree order, or
+    (code, None, None) for a set with a code (host only; nothing is written
+    into the shreds)."""
+    from .tile import pack_payloads
+    cnt = len(shreds)
+    root = ctypes.create_string_buffer(32)
+    if not cnt:
+        return _lib.fd_ed25519_hip_fec_root(None, None, None, 0, root, None), None, None
+    buf, off, sz = pack_payloads([bytes(s) for s in shreds])
+    width = 20 * fec_depth(cnt) if cnt <= FEC_SET_MAX else 0
+    proofs = np.zeros(max(1, cnt * width), np.uint8)
+    code = _lib.fd_ed25519_hip_fec_root(_ptr(buf), _ptr(off), _ptr(sz), cnt, root, _ptr(proofs))
+    if code:
+        return code, None, None
+    return code, root.raw, [proofs[width * j:width * (j + 1)].tobytes() for j in range(cnt)]
+
+
 # signed gossip and repair control packets (include/fd_ed25519_hip.h Part 2d)
 PROTO_GOSSIP = 0
 PROTO_REPAIR_SERV = 1
@@ -473,6 +513,47 @@ class Engine:
                                             d_val_first, int(n_val), d_work, d_pkt_out, d_val_out, d_sig_out, d_hash_out,
                                             stream))
 
+    def fec_seal_flat(self, shreds, set_first, privs):
+        """fd_ed25519_hip_fec_seal_host on shreds (a list of raw shreds) whose
+        set k is shreds[set_first[k]:set_first[k + 1]] in tree order; privs is
+        one 32-byte private key per set, one for all, or None (proofs and
+        roots only) -> (int8 code per set, the shreds after the call, uint8
+        [n_set, 32] roots, uint8 [n_set, 64] signatures or None);
+        synchronous."""
+        from .tile import pack_payloads
+        n, n_set = len(shreds), len(set_first) - 1
+        first = _c(set_first, np.uint32)
+        codes, roots = np.zeros(max(1, n_set), np.int8), np.zeros((max(1, n_set), 32), np.uint8)
+        keys = sigs = None
+        if privs is not None:
+            if isinstance(privs, (bytes, bytearray)):
+                privs = [bytes(privs)] * n_set
+            keys = np.frombuffer(b"".join(bytes(k) for k in privs) or bytes(32), np.uint8)
+            assert keys.size == 32 * max(1, n_set)
+            sigs = np.zeros((max(1, n_set), 64), np.uint8)
+        buf, off, sz = pack_payloads([bytes(s) for s in shreds]) if n else (np.zeros(1, np.uint8),) * 3
+        _check(_lib.fd_ed25519_hip_fec_seal_host(self._h, n, _ptr(buf), _ptr(off), _ptr(sz), n_set, _ptr(first), _ptr(keys),
+                                                 _ptr(codes), _ptr(roots), _ptr(sigs)))
+        out = [buf[int(off[i]):int(off[i]) + int(sz[i])].tobytes() for i in range(n)]
+        return codes[:n_set], out, roots[:n_set], (sigs[:n_set] if sigs is not None else None)
+
+    def fec_seal_host(self, sets, privs):
+        """Seals FEC sets (fd_ed25519_hip_fec_seal_host): sets is a list of
+        sets, each the list of its raw shreds in tree order (data, then
+        parity), privs as for fec_seal_flat -> (int8 code per set, the sets
+        with signature and proofs written where the code is 0, roots,
+        signatures or None); synchronous."""
+        first = [0]
+        for s in sets:
+            first.append(first[-1] + len(s))
+        codes, flat, roots, sigs = self.fec_seal_flat([x for s in sets for x in s], first, privs)
+        return codes, [flat[first[k]:first[k + 1]] for k in range(len(sets))], roots, sigs
+
+    def fec_seal_dev(self, n, d_shreds, d_off, d_sz, n_set, d_set_first, d_privs, d_work, d_set_out, d_roots=None,
+                     d_sigs=None, stream=None):
+        """Device-resident fd_ed25519_hip_fec_seal_dev: device addresses (ints); async."""
+        _check(_lib.fd_ed25519_hip_fec_seal_dev(self._h, int(n), d_shreds, d_off, d_sz, int(n_set), d_set_first, d_privs,
+                                                d_work, d_set_out, d_roots, d_sigs, stream))
 
     # ---- batched signing / synthetic workloads -------------------------
     def sign_dev(self, n, d_msgs, d_off, d_sz, d_privs, d_sigs, d_pubs, stream=None):

@@ -212,14 +212,15 @@ typedef struct fd_ed25519_hip_engine fd_ed25519_hip_engine_t;
    setters, latency_set_cpus; 11: Part 2b, the Ed25519 precompile
    instructions of raw transactions; 12: Part 2c, the leader signatures of
    Merkle shreds; 13: Part 2d, signed gossip and repair control packets; 14:
-   Part 2e, the CRDS values of gossip pull responses and push messages).
+   Part 2e, the CRDS values of gossip pull responses and push messages; 15:
+   Part 2f, sealing a leader's FEC sets).
    A consumer checks
    the library it loaded against the header it was built with:
    fd_ed25519_hip_abi_check( FD_ED25519_HIP_ABI_VERSION,
    sizeof(fd_ed25519_hip_slot_t), sizeof(fd_ed25519_hip_info_t),
    sizeof(fd_ed25519_hip_vservice_stats_t) ) returns 0 when they agree,
    FD_ED25519_HIP_ERR_INVAL (with fd_ed25519_hip_last_error) when not. */
-#define FD_ED25519_HIP_ABI_VERSION (14U)
+#define FD_ED25519_HIP_ABI_VERSION (15U)
 
 unsigned
 fd_ed25519_hip_abi_version( void );
@@ -960,6 +961,131 @@ fd_ed25519_hip_crds_host( fd_ed25519_hip_engine_t * engine,
                           signed char *             pkt_out,
                           signed char *             val_out,
                           unsigned char *           hash_out );
+
+/* ---- Part 2f: sealing a leader's FEC sets ------------------------------- */
+
+/* The other half of the shred path.  A leader seals every FEC set before it
+   leaves the box (fd_shredder_next_fec_set, src/disco/shred/fd_shredder.c:
+   225-260): it hashes each data and parity shred into a Merkle leaf, builds
+   the tree of 20-byte nodes over them (fd_bmtree_commit_*,
+   src/ballet/bmtree/fd_bmtree.c:216-348), signs the 32-byte root and copies
+   the signature and each shred's inclusion proof into the shreds -- the
+   inverse of what Part 2c checks.  The entry points below take a batch of
+   sets whose shreds are filled but for those two fields and do all of that
+   on the device.
+
+   A set is cnt shreds in tree order, the data shreds first, then the parity
+   shreds; shred j of the set is leaf j.  A set of no shreds or of more than
+   FEC_SET_MAX gets FEC_ERR_SET and none of its shreds is read.  Otherwise
+   the first shred in set order that fails decides the set's code: one
+   fd_shred_parse rejects gives FEC_ERR_PARSE; one that parses but is no
+   unchained Merkle shred (variant 0x8? data, 0x4? code) FEC_UNSUPPORTED; one
+   whose proof depth (variant & 0xf) is not the shredder's for cnt leaves
+   (fd_bmtree_depth( cnt ) - 1, fd_shredder.c:158), a code shred with
+   data_cnt or code_cnt zero or above 67, or a shred whose header places it
+   elsewhere in the set than j (data: idx - fec_set_idx, code: data_cnt +
+   code.idx) FEC_ERR_SET.  The signature field is an output: Part 2c's
+   rejection of an all-zero signature does not apply.  A set with a code has
+   no byte of any of its shreds written and does not affect any other set.
+   A sealed set's shreds all get 0 from fd_ed25519_hip_shreds_dev under the
+   key's public key.  All four codes are this library's; they reuse Part
+   2c's numbering.
+
+   Out of scope: the Reed-Solomon parity itself (the caller hands in filled
+   parity shreds, as fd_shredder.c:167-223 produces them before the tree),
+   the construction of shred headers, and chained and resigned variants,
+   which the reference's shredder does not emit. */
+#define FD_ED25519_HIP_FEC_OK          (  0)
+#define FD_ED25519_HIP_FEC_ERR_PARSE   (-16)
+#define FD_ED25519_HIP_FEC_UNSUPPORTED (-18)
+#define FD_ED25519_HIP_FEC_ERR_SET     (-19)
+#define FD_ED25519_HIP_FEC_SET_MAX     (134UL)   /* 67 data + 67 parity shreds */
+
+/* The root of one set and, optionally, its proofs, host only (no GPU), from
+   the same source as the device's tree kernel.  Shred j of the set is
+   shreds[shred_off[j] .. shred_off[j] + shred_sz[j]), j < cnt.  Returns 0
+   with root[0..32) written and, when proofs is not NULL, leaf j's proof
+   nodes at proofs + 20 depth j (depth = 0 for cnt 1, else the bits of cnt-1);
+   else the set's code, root and proofs untouched.  The shreds are only
+   read, shred j its bytes [0, shred_sz[j]). */
+int
+fd_ed25519_hip_fec_root( unsigned char const * shreds,
+                         unsigned long const * shred_off,
+                         unsigned int const *  shred_sz,
+                         unsigned long         cnt,
+                         unsigned char *       root,
+                         unsigned char *       proofs );
+
+/* Device workspace of fec_seal_dev for n shreds in n_set sets: per set the
+   signature (64), its public key (32), the root as the message signed (32),
+   the message's offset (8) and size (4); per shred the set that sealed it
+   (4). */
+#define FD_ED25519_HIP_FEC_WORK_BYTES( n, n_set ) \
+  ( 140UL*(unsigned long)(n_set) + 4UL*(unsigned long)(n) + 16UL )
+
+/* Device-resident batch: every pointer but the engine is a device pointer.
+   Shred i is shreds[shred_off[i] .. shred_off[i] + shred_sz[i]) and may
+   start at any byte; shreds do not overlap.  Set k is the shreds
+   [set_first[k], set_first[k+1]) in tree order (set_first[0]==0,
+   set_first[n_set]==n).  A set_first that is no such prefix sum is
+   survived: a set whose range runs backwards or leaves [0, n) gets
+   FEC_ERR_SET and touches nothing.  privs + 32 k is the private key that
+   signs set k (the array 16-byte aligned), or privs is NULL: then proofs and
+   roots are produced and bytes [0, 64) of every shred are left as they were
+   -- the reference's keyguard split, where the caller has the roots signed
+   elsewhere.
+
+   The shreds are written in place: in a set whose code is 0, bytes [0, 64)
+   of every shred receive the signature of the set's root and the 20 depth
+   bytes that end the shred (at 1203 for data, 1228 for code) its proof;
+   no other byte of the buffer changes, whatever the shreds' alignment.
+   set_out[k] receives the set's code.  roots (optional, 16-byte aligned)
+   receives the root of every sealed set at roots + 32 k, zero for any other;
+   sigs (optional, 16-byte aligned, needs privs) its signature at sigs + 64 k,
+   zero for any other.  work: 16-byte aligned,
+   FD_ED25519_HIP_FEC_WORK_BYTES( n, n_set ) bytes.
+
+   The shred buffer must start 16-byte aligned and stay readable at least 16
+   bytes past the end of the last shred, as for fd_ed25519_hip_shreds_dev.
+   n < 2^32, n_set < 2^31.
+
+   Asynchronous on `stream` (NULL: the engine's): three launches (the tree
+   and the proofs, fd_ed25519_hip_sign_dev's kernel over the roots, the
+   signatures into the shreds; the tree alone without privs); it allocates
+   nothing and does not synchronise.  n_set==0 is a no-op. */
+int
+fd_ed25519_hip_fec_seal_dev( fd_ed25519_hip_engine_t * engine,
+                             unsigned long             n,
+                             unsigned char *           shreds,
+                             unsigned long const *     shred_off,
+                             unsigned int const *      shred_sz,
+                             unsigned long             n_set,
+                             unsigned int const *      set_first,
+                             unsigned char const *     privs,
+                             void *                    work,
+                             signed char *             set_out,
+                             unsigned char *           roots,
+                             unsigned char *           sigs,
+                             void *                    stream );
+
+/* Host-buffer batch, synchronous: packs whole sets into pinned staging
+   memory (in passes, so any n fits), copies, runs fec_seal_dev on a
+   workspace the engine owns and copies back set_out[0..n_set), roots and
+   sigs when not NULL, and into the caller's shreds the signature (with
+   privs) and the proof of every shred of a sealed set -- nothing else.  No
+   alignment is asked of any argument. */
+int
+fd_ed25519_hip_fec_seal_host( fd_ed25519_hip_engine_t * engine,
+                              unsigned long             n,
+                              unsigned char *           shreds,
+                              unsigned long const *     shred_off,
+                              unsigned int const *      shred_sz,
+                              unsigned long             n_set,
+                              unsigned int const *      set_first,
+                              unsigned char const *     privs,
+                              signed char *             set_out,
+                              unsigned char *           roots,
+                              unsigned char *           sigs );
 
 /* ---- Part 3: batched signing and the synthetic workload generator ------ */
 
