@@ -19,7 +19,7 @@
             other than success, else 0, and the optional verify codes; per
             packet its code
      hash   only when asked for, one lane per value: SHA-256 of the value's
-            own bytes (fd_sha256_dev.h's block function and loaders) */
+            own bytes (fd_sha256_dev.h's sha256_bytes) */
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "../../include/fd_ed25519_hip.h"
@@ -126,30 +126,6 @@ fd_ed25519_crds_finish_kernel(fd_ed25519_crds_finish_params_t p) {
   if (p.sig_out) p.sig_out[k] = (int8_t)sig;
 }
 
-/* h = SHA-256( s[0..total) ) as eight big-endian words, total >= 1; the
-   loads are fd_sha256_dev.h's: dword-aligned 16-byte chunks that may read up
-   to 15 bytes past the last byte (the packet buffer is readable 16 bytes
-   past its end) */
-__device__ static inline void crds_sha256(uint32_t (&h)[8], const uint8_t* s, uint32_t total) {
-  const uintptr_t a = reinterpret_cast<uintptr_t>(s);
-  sha256_src m;
-  m.base = reinterpret_cast<const uint32_t*>(a & ~(uintptr_t)3);
-  m.shift = (uint32_t)(a & 3);
-  m.total = total;
-  const uint32_t nblk = (total + 9u + 63u) >> 6;
-  sha256_init(h);
-  uint4 cur[SHA256_CHUNKS];
-  uint32_t w[16];
-  sha256_load_block(cur, m, 0u);
-#pragma clang loop unroll(disable)
-  for (uint32_t b = 0; b < nblk; b++) {
-    if (64u * b + 64u <= total) sha256_build_w<true>(w, cur, m, b, nblk);
-    else sha256_build_w<false>(w, cur, m, b, nblk);
-    if (b + 1 < nblk) sha256_load_block(cur, m, b + 1);
-    sha256_block(h, w);
-  }
-}
-
 __global__ void __launch_bounds__(FD_CRDS_STAGE_BLOCK)
 fd_ed25519_crds_hash_kernel(fd_ed25519_crds_hash_params_t p) {
   const uint64_t k = (uint64_t)blockIdx.x * FD_CRDS_STAGE_BLOCK + threadIdx.x;
@@ -158,7 +134,7 @@ fd_ed25519_crds_hash_kernel(fd_ed25519_crds_hash_params_t p) {
   const uint32_t vsz = p.val_sz[k];
   uint32_t h[8];
   if (vsz) {
-    crds_sha256(h, p.pkts + p.msg_off[k] - 64, 64u + vsz);   /* the signature lies in front of the data */
+    sha256_bytes(h, p.pkts + p.msg_off[k] - 64, 64u + vsz);   /* the signature lies in front of the data */
 #pragma unroll
     for (int q = 0; q < 8; q++) out[q] = __builtin_bswap32(h[q]);
   } else {

@@ -367,6 +367,14 @@ int fd_ed25519_hip_private_diag_dsm( struct fd_ed25519_hip_engine * e, int form,
                                      unsigned char const * pflag, int32_t const * pts, uint32_t const * hs,
                                      uint32_t const * k, unsigned char const * S, signed char * out );
 
+/* The device hashes take a message's remaining byte count as a signed
+   32-bit value (fd_sha512_dev.h sha_msg_dword: (int)sz - p), so a message
+   the device hashes is at most FD_ED25519_HIP_MSG_SZ_MAX (2^31 - 1) bytes.
+   FD_ED25519_HIP_ERR_INVAL when one of msg_sz[0..n) is larger, else 0; host
+   only (no engine, no GPU, no allocation): what the host-buffer entry
+   points run before they stage anything (tests/test_hash_diag_selfcheck.py). */
+int fd_ed25519_hip_private_msg_sz_check( unsigned int const * msg_sz, unsigned long n );
+
 /* ---- raw transactions (fd_ed25519_txn.hip) ---- */
 
 /* per-transaction code for a payload fd_txn_parse rejects (never an

@@ -141,6 +141,31 @@ FD_DEV void sha256_build_w(uint32_t (&w)[16], const uint4 (&c)[SHA256_CHUNKS], c
   }
 }
 
+/* h = SHA-256( s[0..total) ) as eight big-endian words, total >= 1 (the
+   CRDS value hash, fd_ed25519_crds.hip); the loads are the leaf's:
+   dword-aligned 16-byte chunks that may read up to 15 bytes past the last
+   byte (the packet buffer is readable 16 bytes past its end).  Not
+   FD_DEV: the compiler keeps its choice of inlining the chain of blocks. */
+__device__ static inline void sha256_bytes(uint32_t (&h)[8], const uint8_t* s, uint32_t total) {
+  const uintptr_t a = reinterpret_cast<uintptr_t>(s);
+  sha256_src m;
+  m.base = reinterpret_cast<const uint32_t*>(a & ~(uintptr_t)3);
+  m.shift = (uint32_t)(a & 3);
+  m.total = total;
+  const uint32_t nblk = (total + 9u + 63u) >> 6;
+  sha256_init(h);
+  uint4 cur[SHA256_CHUNKS];
+  uint32_t w[16];
+  sha256_load_block(cur, m, 0u);
+#pragma clang loop unroll(disable)
+  for (uint32_t b = 0; b < nblk; b++) {
+    if (64u * b + 64u <= total) sha256_build_w<true>(w, cur, m, b, nblk);
+    else sha256_build_w<false>(w, cur, m, b, nblk);
+    if (b + 1 < nblk) sha256_load_block(cur, m, b + 1);
+    sha256_block(h, w);
+  }
+}
+
 /* h = SHA-256( leaf prefix || s[64 .. 64 + leaf_sz) ) as eight big-endian
    words; leaf_sz >= 38 (it is 839 at least), so block 0 is full */
 FD_DEV void sha256_leaf(uint32_t (&h)[8], const uint8_t* s, uint32_t leaf_sz) {

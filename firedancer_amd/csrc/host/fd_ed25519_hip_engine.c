@@ -1258,12 +1258,20 @@ upload_and_verify( fd_ed25519_hip_engine_t * e, uint64_t n, uint64_t msg_bytes )
 }
 
 int
+fd_ed25519_hip_private_msg_sz_check( unsigned int const * msg_sz, unsigned long n ) {
+  if( !msg_sz ) return n ? FD_ED25519_HIP_ERR_INVAL : FD_ED25519_HIP_OK;
+  for( unsigned long i=0UL; i<n; i++ ) if( msg_sz[i]>FD_ED25519_HIP_MSG_SZ_MAX ) return FD_ED25519_HIP_ERR_INVAL;
+  return FD_ED25519_HIP_OK;
+}
+
+int
 fd_ed25519_hip_verify_host( fd_ed25519_hip_engine_t * e, unsigned long n,
                             unsigned char const * msgs, unsigned long const * msg_off, unsigned int const * msg_sz,
                             unsigned char const * sigs, unsigned char const * pubs, signed char * out ) {
   if( !e ) return FD_ED25519_HIP_ERR_INVAL;
   if( !n ) return FD_ED25519_HIP_OK;
   if( !msg_off || !msg_sz || !sigs || !pubs || !out ) return FD_ED25519_HIP_ERR_INVAL;
+  if( fd_ed25519_hip_private_msg_sz_check( msg_sz, n ) ) return FD_ED25519_HIP_ERR_INVAL;
   HIPCHK( hipSetDevice( e->device ), "hipSetDevice" );
   int err;
   if( (err = stage_sigs( e, n )) ) return err;
@@ -1296,6 +1304,7 @@ fd_ed25519_hip_verify_txns_host( fd_ed25519_hip_engine_t * e, unsigned long ntxn
   if( !e ) return FD_ED25519_HIP_ERR_INVAL;
   if( !ntxn ) return FD_ED25519_HIP_OK;
   if( !txn_msg_off || !txn_msg_sz || !txn_first || !txn_cnt || !out_txn ) return FD_ED25519_HIP_ERR_INVAL;
+  if( fd_ed25519_hip_private_msg_sz_check( txn_msg_sz, ntxn ) ) return FD_ED25519_HIP_ERR_INVAL;
   HIPCHK( hipSetDevice( e->device ), "hipSetDevice" );
   /* signatures actually verified: those of transactions with 1..16 signers
      (others are ERR_SIG without reading their inputs, as the reference) */
@@ -2026,16 +2035,18 @@ typedef struct dropin_req {
 
 /* Messages of at least this many bytes are hashed on the host by the
    calling thread (fd_ed25519_hip_private_challenge) and verified from their
-   digests: the device path's message sizes are 32-bit, and the reference
-   takes any ulong size (src/ballet/ed25519/fd_ed25519.h:96-101).  A test
-   hook moves the limit down (fd_ed25519_hip_dropin_set_host_hash_min). */
-static unsigned long dropin_host_hash_min = 1UL<<32;
+   digests: the device hash takes sizes up to FD_ED25519_HIP_MSG_SZ_MAX
+   (2^31 - 1: its remaining-byte counts are signed 32-bit values), and the
+   reference takes any ulong size (src/ballet/ed25519/fd_ed25519.h:96-101).
+   A test hook moves the limit down (fd_ed25519_hip_dropin_set_host_hash_min). */
+#define DROPIN_HOST_HASH_MIN_MAX ((unsigned long)FD_ED25519_HIP_MSG_SZ_MAX + 1UL)
+static unsigned long dropin_host_hash_min = DROPIN_HOST_HASH_MIN_MAX;
 
-/* clamped to 4 GiB: a limit above that would leave messages the device's
-   32-bit sizes cannot carry on the device path */
+/* clamped to 2 GiB: a limit above that would leave messages the device
+   hash cannot carry on the device path */
 void
 fd_ed25519_hip_dropin_set_host_hash_min( unsigned long bytes ) {
-  dropin_host_hash_min = ( bytes && bytes<(1UL<<32) ) ? bytes : 1UL<<32;
+  dropin_host_hash_min = ( bytes && bytes<DROPIN_HOST_HASH_MIN_MAX ) ? bytes : DROPIN_HOST_HASH_MIN_MAX;
 }
 
 void fd_ed25519_hip_private_challenge( unsigned char const sig[ 64 ], unsigned char const pub[ 32 ],
@@ -2552,9 +2563,9 @@ fd_ed25519_hip_dropin_reset( void ) {
   return err;
 }
 
-/* The device path carries message sizes as 32-bit values; the reference
+/* The device hash takes message sizes below 2^31; the reference
    takes any ulong size.  A message of dropin_host_hash_min bytes or more
-   (4 GiB: the first size the device cannot carry) is hashed here, in the
+   (2 GiB: the first size the device hash cannot carry) is hashed here, in the
    calling thread, with the library's own SHA-512 (one digest of R_j||A_j||M
    per signature), before the request is queued; everything after the hash
    -- the reduction mod L, decompression, the group equation, the batch
@@ -2563,8 +2574,8 @@ fd_ed25519_hip_dropin_reset( void ) {
 static void
 dropin_prepare( dropin_req_t * r ) {
   /* the second test is the guard whatever the limit says: a size the
-     device path would truncate is never sent there */
-  r->hashed = r->msg_sz>=dropin_host_hash_min || r->msg_sz>(unsigned long)UINT32_MAX;
+     device hash cannot carry is never sent there */
+  r->hashed = r->msg_sz>=dropin_host_hash_min || r->msg_sz>(unsigned long)FD_ED25519_HIP_MSG_SZ_MAX;
   if( !r->hashed ) return;
   for( unsigned int j=0U; j<r->cnt; j++ )
     fd_ed25519_hip_private_challenge( r->sigs + 64UL*j, r->pubs + 32UL*j, r->msg, r->msg_sz, r->dig[ j ] );

@@ -4,7 +4,7 @@
    drop-in or of a pipe's batch, host/fd_ed25519_hip_hsrec.cc): the scalars
    start from this digest, and a launch whose k has no half-size pair hands
    it to the device.  And the drop-in verify of a message whose size does
-   not fit the device path's 32-bit message sizes (4 GiB and more; the
+   not fit the device hash's signed 32-bit byte counts (2 GiB and more; the
    reference takes any ulong size, src/ballet/ed25519/fd_ed25519.h:96-101):
    the device takes the digest from there
    (fd_ed25519_hip_verify_digests_dev), reduction mod L, decompression and

@@ -50,7 +50,7 @@ typedef struct fd_sha512_private fd_sha512_t;
    policy decides (fd_ed25519_hip_dropin_set_on_lost below: abort with a
    message, the default, or fail closed); this path never falls back to
    the CPU.  Any
-   msg_sz is accepted, as by the reference (4 GiB and more: the message is
+   msg_sz is accepted, as by the reference (2 GiB and more: the message is
    hashed on the host, fd_ed25519_hip_dropin_set_host_hash_min). */
 int
 fd_ed25519_verify( unsigned char const   msg[],
@@ -89,12 +89,12 @@ fd_ed25519_strerror( int err );
 void
 fd_ed25519_hip_dropin_stats( unsigned long * launches, unsigned long * requests );
 
-/* A message of 4 GiB or more does not fit the device path's 32-bit message
-   sizes: the drop-ins hash it (R_j || A_j || M per signature) on the
+/* A message of 2 GiB or more is past what the device hash takes
+   (FD_ED25519_HIP_MSG_SZ_MAX below): the drop-ins hash it (R_j || A_j || M per signature) on the
    calling thread with the library's SHA-512 and verify the rest on the GPU
    from the digests (fd_ed25519_hip_verify_digests_dev); no message is ever
    truncated or refused.  Test hook: messages of at least `bytes` bytes take
-   that path (0 restores 4 GiB). */
+   that path (0 restores 2 GiB, and so does a limit above it). */
 void
 fd_ed25519_hip_dropin_set_host_hash_min( unsigned long bytes );
 
@@ -350,7 +350,17 @@ fd_ed25519_hip_engine_stream( fd_ed25519_hip_engine_t * engine );
    start at any byte, and the message buffer must stay readable at least 16
    bytes past the end of the last message (the SHA-512 loader reads aligned
    16-byte granules, up to 15 bytes beyond a message's last byte; the same
-   holds for fd_ed25519_hip_sign_dev / _gen_dev).  Enqueued on `stream` (NULL = the engine's stream) and
+   holds for fd_ed25519_hip_sign_dev / _gen_dev).  Every msg_sz[i] must be
+   at most FD_ED25519_HIP_MSG_SZ_MAX (2^31 - 1): the device hashes take a
+   message's remaining byte count as a signed 32-bit value, and a larger
+   size gives a wrong digest (a wrong verdict), never a wild read.  The
+   sizes here are device memory, so this entry point and _sign_dev cannot
+   check them: the bound is the caller's.  fd_ed25519_hip_verify_host and
+   _verify_txns_host return FD_ED25519_HIP_ERR_INVAL for a larger size
+   before they stage anything, the drop-ins hash such a message on the
+   host, the raw-input fronts (Parts 2b-2f) hash at most a packet, a
+   shred or a 32-byte root, and a pipe's or pool's messages lie inside the
+   msg_cap its creator chose (keep that below 2 GiB).  Enqueued on `stream` (NULL = the engine's stream) and
    returns immediately; the engine's work arrays are reused by the next
    call, so calls on one engine must be ordered on one stream.  A call of
    more than max_chunk signatures alternates its chunks between two sets of
@@ -364,6 +374,8 @@ fd_ed25519_hip_engine_stream( fd_ed25519_hip_engine_t * engine );
    no call allocates device memory or fails for lack of it; a smaller
    engine allocates it on its first multi-chunk call (one hipMalloc, which
    may synchronise the device once). */
+#define FD_ED25519_HIP_MSG_SZ_MAX 0x7fffffffU
+
 int
 fd_ed25519_hip_verify_dev( fd_ed25519_hip_engine_t * engine,
                            unsigned long             n,

@@ -4,15 +4,21 @@ and the exact references its tests compare with: integers mod p and mod L,
 affine Edwards arithmetic, limb <-> value conversion for the one-lane
 radix-2^25.5 form and the lane-split radix-2^16 form, and the operand
 classes (limb vectors at the documented bounds, special values in several
-representations, scalar edge lists).  Test infrastructure, no product code.
+representations, scalar edge lists); and for the hash family
+(diag/fd_ed25519_diag_hash.hip) the byte-buffer layout, the case builders
+and hashlib's digests in the word order the device returns.  Test
+infrastructure, no product code.
 
 Everything here is exact: Python integers, no tolerances."""
 import ctypes
+import hashlib
 import os
+import random
 
 import numpy as np
 
 import bounds_model as bm
+import shred_model
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 # $FD_ED25519_DIAG_LIB: another build of the unit (as $FD_ED25519_HIP_LIB for the product), e.g. one
@@ -53,6 +59,14 @@ class Diag:
             f = getattr(self.lib, "fd_ed25519_diag_" + fam)
             f.argtypes = [ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_ulong]
             f.restype = ctypes.c_int
+        self.lib.fd_ed25519_diag_hash.argtypes = [ctypes.c_int, ctypes.c_void_p, ctypes.c_ulong, ctypes.c_void_p,
+                                                  ctypes.c_void_p, ctypes.c_ulong]
+        self.lib.fd_ed25519_diag_hash.restype = ctypes.c_int
+
+    def raw_hash(self, opnum, buf, inp, out, n, buf_sz=None):
+        """fd_ed25519_diag_hash as it is: buf a uint8 array, inp / out uint32 arrays; the HIP error code"""
+        return self.lib.fd_ed25519_diag_hash(int(opnum), buf.ctypes.data, len(buf) if buf_sz is None else int(buf_sz),
+                                             inp.ctypes.data, out.ctypes.data, int(n))
 
     def raw(self, family, opnum, inp, out, n):
         return getattr(self.lib, "fd_ed25519_diag_" + family)(int(opnum), inp.ctypes.data, out.ctypes.data, int(n))
@@ -393,3 +407,284 @@ def scalar_edges_lt_l(rng, n_random=300):
     xs += [rng.randrange(L) for _ in range(n_random)]
     assert all(0 <= x < L for x in xs)
     return xs
+
+
+# ---- the hash family (diag/fd_ed25519_diag_hash.hip) ---------------------------
+
+# the op numbers of fd_ed25519_diag_hash.hip's enum, in order
+HASH_OPS = ("sha512_pre8", "sha512_ram", "sha512_ram_2w", "sha256_bytes", "sha256_leaf", "sha256_node",
+            "sha256_node_pair")
+HASH_IN, HASH_OUT = 24, 16
+HASH_PAD = 16                      # filler bytes in front of and behind every message
+HASH_MAX_N, HASH_MAX_BUF = 1 << 20, 1 << 28
+HIP_ERROR_UNKNOWN = 999            # the entry point's "a lane past n stored"
+LEAF_PREFIX, NODE_PREFIX = shred_model.LEAF, shred_model.NODE
+SHA512_OPS = {"sha512_pre8": 32, "sha512_ram": 64, "sha512_ram_2w": 64}     # op -> prefix bytes
+SHA512_SIZES = list(range(601)) + [1232, 1233, 65535, 65536, 65537]
+LEAF_REAL_SIZES = [1115 - 20 * d + x for d in range(16) for x in (0x18, 0x19)]   # fd_shred_core.h: P
+
+
+def hash_per_block(op):
+    """cases a block serves: case i is lane i % per of block i // per"""
+    return 32 if op == "sha512_ram_2w" else 64
+
+
+def sha512_blocks(total):
+    """FIPS 180-4 5.1.2: 0x80, zeros, 128-bit length"""
+    return (total + 17 + 127) // 128
+
+
+def sha256_blocks(total):
+    """FIPS 180-4 5.1.1: 0x80, zeros, 64-bit length"""
+    return (total + 9 + 63) // 64
+
+
+def sha512_full_blocks(pre, sz):
+    """blocks of prefix || message that are message bytes from end to end"""
+    return sum(1 for b in range(sha512_blocks(pre + sz)) if 128 * b >= pre and 128 * b + 128 <= pre + sz)
+
+
+class HashBuf:
+    """The byte buffer of one launch: every message is placed at the next
+    offset of the wanted byte shift (offset % 4; the device allocation is
+    256-byte aligned) with at least `lead` bytes of filler in front of it and
+    HASH_PAD behind, so the bytes next to a message are never another
+    case's.  `spans` records (start, end) of every message."""
+
+    def __init__(self):
+        self.parts, self.end, self.spans = [], 0, []
+
+    def place(self, data, shift, lead=HASH_PAD):
+        off = self.end + lead
+        off += (shift - off) % 4
+        self.parts.append((off, bytes(data)))
+        self.spans.append((off, off + len(data)))
+        self.end = off + len(data)
+        return off
+
+    def size(self):
+        return self.end + HASH_PAD
+
+    def bytes(self, filler):
+        buf = np.full(self.size(), filler, np.uint8)
+        for off, data in self.parts:
+            buf[off:off + len(data)] = np.frombuffer(data, np.uint8)
+        return buf
+
+
+def le_words(b):
+    return [int(x) for x in np.frombuffer(b, "<u4")]
+
+
+def be_words(b):
+    return [int(x) for x in np.frombuffer(b, ">u4")]
+
+
+def hash_case(op, off, sz, shift, want, opnd=(), flag=0, note=""):
+    """want: the 16 (SHA-512, little-endian) or 8 (SHA-256, big-endian)
+    words the device returns for the reference digest"""
+    assert off % 4 == shift or op == "sha256_node_pair"
+    return dict(op=op, off=off, sz=sz, shift=shift, flag=flag, opnd=list(opnd), want=want, note=note)
+
+
+def hash_bounds_ok(c, buf_sz):
+    """the entry point's own rule: the bytes a case reads lie inside [0, buf_sz)"""
+    op, off, sz = c["op"], c["off"], c["sz"]
+    if op in SHA512_OPS:
+        return off + sz <= buf_sz
+    if op == "sha256_bytes":
+        return sz >= 1 and off + sz <= buf_sz
+    if op == "sha256_leaf":
+        return sz >= 38 and off + 64 + sz <= buf_sz
+    if op == "sha256_node":
+        return off + 20 <= buf_sz
+    return op == "sha256_node_pair"
+
+
+def _rand_bytes(rng, n):
+    return rng.getrandbits(8 * n).to_bytes(n, "little") if n else b""
+
+
+def sha512_prefix(rng, kind, nbytes):
+    """prefix rows: random, all-zero and all-ones words"""
+    return {"zero": bytes(nbytes), "ones": b"\xff" * nbytes}.get(kind) or _rand_bytes(rng, nbytes)
+
+
+def sha512_cases(op, sizes_shifts, rng, buf, kinds=None):
+    """one case per (size, shift) in the order given; the prefix is operand
+    words [0, prefix / 4)"""
+    pre_sz = SHA512_OPS[op]
+    cases = []
+    for i, (sz, shift) in enumerate(sizes_shifts):
+        kind = kinds[i] if kinds else rng.choice(("zero", "ones") + ("random",) * 6)
+        pre, msg = sha512_prefix(rng, kind, pre_sz), _rand_bytes(rng, sz)
+        off = buf.place(msg, shift)
+        cases.append(hash_case(op, off, sz, shift, le_words(hashlib.sha512(pre + msg).digest()), le_words(pre),
+                               note=kind))
+    return cases
+
+
+def sha512_sweep(op, seed=71):
+    """every size of SHA512_SIZES at every byte shift, laid out in size order
+    (buffer, cases sorted by size: near-uniform waves, as the length sort
+    gives them)"""
+    rng = random.Random(seed)
+    buf = HashBuf()
+    cases = sha512_cases(op, [(sz, sh) for sz in SHA512_SIZES for sh in range(4)], rng, buf)
+    return buf, cases
+
+
+def shuffled(cases, seed=72):
+    """a seeded shuffle of the same cases: divergent waves"""
+    out = list(cases)
+    random.Random(seed).shuffle(out)
+    return out
+
+
+def sha512_wave_compositions(op, seed=77):
+    """(buffer, cases, names): whole blocks of chosen sizes, one composition
+    a block (64 cases in the one-wave form, 32 in the two-wave form), lane l
+    at byte shift l % 4.  The all-empty block comes last: in the two-wave
+    form every wave also runs to case n - 1's block count, which so adds
+    nothing to any composition."""
+    per = hash_per_block(op)
+    lanes = (0, 15, 31) if per == 32 else (0, 31, 32, 63)
+    comps = [(f"all lanes {sz} bytes", [sz] * per) for sz in (47, 48, 304)]
+    comps.append(("ascending with the lane", [600 * l // (per - 1) for l in range(per)]))
+    comps.append(("descending with the lane", [600 * (per - 1 - l) // (per - 1) for l in range(per)]))
+    for at in lanes:
+        comps.append((f"one 600-byte lane at {at} among empty messages", [600 if l == at else 0 for l in range(per)]))
+        comps.append((f"one empty message at lane {at} among 600-byte ones", [0 if l == at else 600 for l in range(per)]))
+    comps.append(("all lanes 0 bytes", [0] * per))
+    rng = random.Random(seed)
+    buf, cases = HashBuf(), []
+    for name, sizes in comps:
+        blk = sha512_cases(op, [(sz, l % 4) for l, sz in enumerate(sizes)], rng, buf)
+        for c in blk:
+            c["note"] = name
+        cases += blk
+    return buf, cases, [name for name, _ in comps]
+
+
+def sha512_dead_lane_cases(n, last, seed=78):
+    """n cases of the two-wave form whose last case (the one dead lanes
+    repeat, and whose block count every wave runs to) is the longest or the
+    shortest of its block"""
+    rng = random.Random(seed + n)
+    body = [0, 47, 48, 175, 176, 303, 304, 431, 432]
+    sizes = [body[i % len(body)] + (64 if last == "shortest" else 0) for i in range(n - 1)]
+    sizes.append(600 if last == "longest" else 0)
+    buf = HashBuf()
+    return buf, sha512_cases("sha512_ram_2w", [(sz, i % 4) for i, sz in enumerate(sizes)], rng, buf)
+
+
+def sha256_bytes_sweep(seed=73):
+    rng = random.Random(seed)
+    buf, cases = HashBuf(), []
+    for sz in range(1, 301):
+        for shift in range(4):
+            msg = _rand_bytes(rng, sz)
+            cases.append(hash_case("sha256_bytes", buf.place(msg, shift), sz, shift,
+                                   be_words(hashlib.sha256(msg).digest())))
+    return buf, cases
+
+
+def sha256_leaf_sweep(seed=74):
+    """leaf_sz 38..300 and the real leaf sizes at every shift.  The case's
+    offset is 64 bytes in front of the leaf data (a shred's start); the 26
+    bytes in front of the data, which the function loads and replaces with
+    the prefix, are filler: the data is placed with 64 + HASH_PAD bytes of
+    filler in front."""
+    rng = random.Random(seed)
+    buf, cases = HashBuf(), []
+    for sz in list(range(38, 301)) + LEAF_REAL_SIZES:
+        for shift in range(4):
+            data = _rand_bytes(rng, sz)
+            at = buf.place(data, shift, lead=64 + HASH_PAD)
+            cases.append(hash_case("sha256_leaf", at - 64, sz, shift,
+                                   be_words(hashlib.sha256(LEAF_PREFIX + data).digest())))
+    return buf, cases
+
+
+CHILD_CLASSES = ("random", "zero", "ones", "top", "lo16", "hi16")
+
+
+def child_words(rng, cls):
+    """five big-endian words of a 20-byte Merkle node; lo16 / hi16 are for the
+    16-bit funnel shifts and x[0] >> 16"""
+    if cls == "random":
+        return [rng.getrandbits(32) for _ in range(5)]
+    return [{"zero": 0, "ones": 0xffffffff, "top": 0x80000000, "lo16": 0x0000ffff, "hi16": 0xffff0000}[cls]] * 5
+
+
+def words_be_bytes(w):
+    return b"".join(int(x).to_bytes(4, "big") for x in w)
+
+
+def sha256_node_sweep(seed=75):
+    """(buffer, node cases, pair cases): every class of running node x every
+    class of sibling x sibling shift x right; pair case i has the same two
+    children as node case i.  A node case's operand is the running node's
+    five words; the test appends words 5..7."""
+    rng = random.Random(seed)
+    buf, nodes, pairs = HashBuf(), [], []
+    for ca in CHILD_CLASSES:
+        for cb in CHILD_CLASSES:
+            for shift in range(4):
+                for right in (0, 1):
+                    h, s = child_words(rng, ca), child_words(rng, cb)
+                    left, rgt = (s, h) if right else (h, s)
+                    want = be_words(hashlib.sha256(NODE_PREFIX + words_be_bytes(left) + words_be_bytes(rgt)).digest())
+                    off = buf.place(words_be_bytes(s), shift)
+                    note = f"node {ca}, sibling {cb}"
+                    nodes.append(hash_case("sha256_node", off, 20, shift, want, h, flag=right, note=note))
+                    pairs.append(hash_case("sha256_node_pair", 0, 0, 0, want, left + rgt, flag=right, note=note))
+    return buf, nodes, pairs
+
+
+def hash_rows(cases):
+    inp = np.zeros((max(len(cases), 1), HASH_IN), np.uint32)
+    for i, c in enumerate(cases):
+        inp[i, 0], inp[i, 1], inp[i, 2] = c["off"], c["sz"], c["flag"]
+        inp[i, 4:4 + len(c["opnd"])] = c["opnd"]
+    return inp
+
+
+OUT_FILL = 0x5a5aa5a5
+
+
+def run_hash(diag, op, buf, cases, extra_rows=0):
+    """one launch: the (n + extra_rows, 16) out array, which went in filled
+    with OUT_FILL (rows past n belong to the caller and must come back so)"""
+    n = len(cases)
+    assert all(c["op"] == op for c in cases)
+    inp = hash_rows(cases)
+    out = np.full((max(n, 1) + extra_rows, HASH_OUT), OUT_FILL, np.uint32)
+    rc = diag.raw_hash(HASH_OPS.index(op), buf, inp, out, n)
+    assert rc == 0, f"fd_ed25519_diag_hash({op}) returned HIP error {rc}"
+    return out
+
+
+def hash_describe(cases, i):
+    """where case i ran: op, size, shift, lane, and its wave's composition"""
+    c = cases[i]
+    per = hash_per_block(c["op"])
+    blk = cases[i - i % per:i - i % per + per]
+    sizes = [x["sz"] for x in blk]
+    comp = f"block {i // per} of {len(blk)} cases, sizes {min(sizes)}..{max(sizes)}"
+    if len(set(sizes)) > 1:
+        comp += f" (lanes {[s for s in sizes[:8]]}...)"
+    if c["op"] == "sha512_ram_2w":
+        comp += f", case n-1 of {len(cases)} has {cases[-1]['sz']} bytes"
+    return (f"{c['op']}: sz {c['sz']}, shift {c['shift']}, case {i} = lane {i % per} of {comp}"
+            + (f", right {c['flag']}" if c["op"] == "sha256_node" else "") + (f" [{c['note']}]" if c["note"] else ""))
+
+
+def hash_mismatches(cases, out):
+    """descriptions of the cases whose words differ from hashlib's"""
+    bad = []
+    for i, c in enumerate(cases):
+        w = c["want"]
+        if [int(x) for x in out[i, :len(w)]] != w:
+            bad.append(hash_describe(cases, i))
+    return bad

@@ -56,6 +56,51 @@ def test_sign_dev_matches_sign_kat(fd, eng):
         assert sigs[i].tobytes().hex() == k["sig"], i
 
 
+def test_sign_dev_at_hash_edges(fd, eng, oracle):
+    """sign_dev hashes prefix || M (sha512_pre<8>, block-count edges at 79/80,
+    207/208, 335/336, 463/464 bytes) and R || A || M (edges at 47/48,
+    175/176, 303/304, 431/432) in the same lane: every size around both sets
+    of edges at every message byte shift, four private keys, one launch; the
+    last message ends 16 bytes before the end of the allocation, the
+    readable tail the loaders are promised.  Signature and public key equal
+    the oracle's byte for byte."""
+    import random
+    rng = random.Random(4242)
+    sizes = list(range(0, 97)) + list(range(170, 216)) + list(range(296, 346)) + list(range(425, 471)) + [1232]
+    privs = [bytes(rng.getrandbits(8) for _ in range(32)) for _ in range(4)]
+    cases, buf = [], bytearray()
+    for sz in sizes:
+        for shift in range(4):
+            buf += bytes(rng.getrandbits(8) for _ in range((shift - len(buf)) % 4))
+            cases.append((len(buf), sz, shift, len(cases) % 4))
+            buf += bytes(rng.getrandbits(8) for _ in range(sz))
+    n = len(cases)
+    assert n == 960 and all(o % 4 == sh for o, _, sh, _ in cases)
+    off = np.array([c[0] for c in cases], np.uint64)
+    sz = np.array([c[1] for c in cases], np.uint32)
+    pr = np.frombuffer(b"".join(privs[c[3]] for c in cases), np.uint8)
+    d_m = eng.alloc(len(buf) + 16).upload(np.frombuffer(bytes(buf), np.uint8))
+    assert d_m.ptr % 4 == 0     # the shifts are the offsets'
+    d_off, d_sz, d_pr = eng.alloc(8 * n).upload(off), eng.alloc(4 * n).upload(sz), eng.alloc(32 * n).upload(pr)
+    d_sig, d_pub = eng.alloc(64 * n), eng.alloc(32 * n)
+    eng.sign_dev(n, d_m.ptr, d_off.ptr, d_sz.ptr, d_pr.ptr, d_sig.ptr, d_pub.ptr)
+    eng.sync()
+    sigs = d_sig.download(np.uint8, 64 * n).reshape(n, 64)
+    pubs = d_pub.download(np.uint8, 32 * n).reshape(n, 32)
+    want_pub = []
+    for p in privs:
+        pub = ctypes.create_string_buffer(32)
+        oracle.oracle_ed25519_public_from_private(pub, p)
+        want_pub.append(pub.raw)
+    for i, (o, s, shift, k) in enumerate(cases):
+        where = f"sz {s}, shift {shift}, key {k}, lane {i % 64} of wave {i // 64}"
+        assert pubs[i].tobytes() == want_pub[k], where
+        m = bytes(buf[o:o + s])
+        sig = ctypes.create_string_buffer(64)
+        oracle.oracle_ed25519_sign(sig, m, s, want_pub[k], privs[k])
+        assert sigs[i].tobytes() == sig.raw, where
+
+
 def test_generator_matches_host_definition_and_oracle(fd, eng, oracle):
     from firedancer_amd import workload
     seed, base, n = 1234, 5000, 1024
