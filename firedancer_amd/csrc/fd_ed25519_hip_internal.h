@@ -367,6 +367,52 @@ int fd_ed25519_hip_private_diag_dsm( struct fd_ed25519_hip_engine * e, int form,
                                      unsigned char const * pflag, int32_t const * pts, uint32_t const * hs,
                                      uint32_t const * k, unsigned char const * S, signed char * out );
 
+/* diagnostic (tests/test_gpu_prep_diag.py), the mirror of diag_dsm: the
+   product's own hash, scalar and decode phases -- and nothing after them --
+   on host inputs, the work arrays they wrote copied back.  form: */
+#define FD_ED25519_DIAG_PREP_WIDE       0   /* small 0: the sort trio (hashed only), hash, scalar and decode kernels */
+#define FD_ED25519_DIAG_PREP_FUSED1     1   /* small 1: prep_kernel                                               */
+#define FD_ED25519_DIAG_PREP_FUSED2     2   /* small 2: prep_kernel                                               */
+#define FD_ED25519_DIAG_PREP_R16        3   /* small 3, full_in_prep 0: prep16's hash and decode blocks           */
+#define FD_ED25519_DIAG_PREP_R16_DECODE 4   /* small 3, hs_host 1: prep16's decode blocks only                    */
+#define FD_ED25519_DIAG_PREP_R16_FULL   5   /* small 3, full_in_prep 1: the full-length items' codes in out too    */
+/*   in: sigs [n][64], pubs [n][32] and either msgs / msg_off [n] / msg_sz
+       [n] (digests NULL: hashed here, perm the sort's in the wide form) or
+       digests [n][64] (msgs unused, perm NULL as the engine sets it); n
+       signatures in arrays of stride cap >= n;
+     out: k [8][cap], sflag [cap], hflag [cap], pflag [2][cap], pts
+       [2][20][cap], hs [19][cap], perm [cap], out [cap] and fix [2 + cap]
+       (fix_cnt, work_ctr, fix_list).
+   Every device temporary behind them is filled with
+   FD_ED25519_DIAG_DSM_UNWRITTEN bytes before the launch, so what no kernel
+   wrote comes back as the pattern -- a row that should have been written,
+   or one at an index >= n.
+   hash_kernel takes perm's entries as indices, so in the wide hashed form
+   the hash phase first runs over a perm of zeros and the sort's result is
+   held to be a permutation of 0 .. n-1 (FD_ED25519_HIP_ERR_INVAL if not,
+   nothing further launched) before the launch proper on the refilled
+   temporaries.
+   diag_prep_check is the whole validation, host only (no engine, no GPU);
+   diag_prep launches nothing it refuses (FD_ED25519_HIP_ERR_INVAL): a form
+   outside 0..5, n == 0 or above n_max (diag_prep passes diag_prep_nmax: what
+   the engine's form limits admit, and for R16_FULL a lane-table slot per
+   signature), cap < n, sigs / pubs / digests NULL or not 16-byte aligned (the
+   rule of fd_ed25519_hip_verify_dev), no digests and no msg_off / msg_sz (or
+   no msgs with a message that has bytes), a msg_sz above
+   FD_ED25519_HIP_MSG_SZ_MAX. */
+int fd_ed25519_hip_private_diag_prep_check( int form, unsigned long n, unsigned long n_max, unsigned long cap,
+                                            unsigned char const * sigs, unsigned char const * pubs,
+                                            unsigned char const * msgs, unsigned long const * msg_off,
+                                            unsigned int const * msg_sz, unsigned char const * digests );
+/* what n_max diag_prep passes for this engine and form (0: the form is not available) */
+unsigned long fd_ed25519_hip_private_diag_prep_nmax( struct fd_ed25519_hip_engine * e, int form );
+int fd_ed25519_hip_private_diag_prep( struct fd_ed25519_hip_engine * e, int form, unsigned long n, unsigned long cap,
+                                      unsigned char const * sigs, unsigned char const * pubs,
+                                      unsigned char const * msgs, unsigned long const * msg_off,
+                                      unsigned int const * msg_sz, unsigned char const * digests,
+                                      uint32_t * k, unsigned char * sflag, unsigned char * hflag, unsigned char * pflag,
+                                      int32_t * pts, uint32_t * hs, uint32_t * perm, signed char * out, uint32_t * fix );
+
 /* The device hashes take a message's remaining byte count as a signed
    32-bit value (fd_sha512_dev.h sha_msg_dword: (int)sz - p), so a message
    the device hashes is at most FD_ED25519_HIP_MSG_SZ_MAX (2^31 - 1) bytes.

@@ -452,7 +452,17 @@ FD_DEV void scalar_one(const fd_ed25519_verify_params_t& p, uint64_t j) {
   uint32_t cw[FD_HALF_TW], dm[FD_HALF_TW];
   int dneg = 0;
   int ok = half_scalars_checked(k, cw, dm, &dneg, p.half_dbits, j);
-  if (!p.sflag[j]) ok = 1;   /* S >= L: decided without the equation, any scalars do */
+  /* no verified pair: what the search ended on (c up to 160 bits, |d| past
+     half_dbits) is never stored -- c = 0, d = 1, so s' = S mod L -- since the
+     half-size loops take whatever an item without the FULL flag holds and
+     size their windows and table indices by it (hsrec stores the same) */
+#pragma unroll
+  for (int w = 0; w < FD_HALF_TW; w++) {
+    cw[w] = ok ? cw[w] : 0u;
+    dm[w] = ok ? dm[w] : (w == 0 ? 1u : 0u);
+  }
+  dneg = ok ? dneg : 0;
+  if (!p.sflag[j]) ok = 1;   /* S >= L: decided without the equation, the scalars above do */
 
   /* s' = d S mod L */
   uint32_t sp[8];

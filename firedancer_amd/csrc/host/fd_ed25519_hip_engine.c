@@ -1009,6 +1009,141 @@ fd_ed25519_hip_private_diag_dsm( fd_ed25519_hip_engine_t * e, int form, unsigned
   return FD_ED25519_HIP_OK;
 }
 
+/* ---- diagnostic: the hash, scalar and decode phases on the caller's inputs,
+        the work arrays read back (fd_ed25519_hip_internal.h;
+        tests/test_gpu_prep_diag.py) ---- */
+
+int
+fd_ed25519_hip_private_diag_prep_check( int form, unsigned long n, unsigned long n_max, unsigned long cap,
+                                        unsigned char const * sigs, unsigned char const * pubs,
+                                        unsigned char const * msgs, unsigned long const * msg_off,
+                                        unsigned int const * msg_sz, unsigned char const * digests ) {
+  if( form<FD_ED25519_DIAG_PREP_WIDE || form>FD_ED25519_DIAG_PREP_R16_FULL ) return FD_ED25519_HIP_ERR_INVAL;
+  if( !n || n>n_max || cap<n ) return FD_ED25519_HIP_ERR_INVAL;
+  if( !sigs || !pubs || ((uintptr_t)sigs & 15UL) || ((uintptr_t)pubs & 15UL) ) return FD_ED25519_HIP_ERR_INVAL;
+  if( digests ) return ((uintptr_t)digests & 15UL) ? FD_ED25519_HIP_ERR_INVAL : FD_ED25519_HIP_OK;
+  if( !msg_off || !msg_sz || fd_ed25519_hip_private_msg_sz_check( msg_sz, n ) ) return FD_ED25519_HIP_ERR_INVAL;
+  if( !msgs ) for( unsigned long i=0UL; i<n; i++ ) if( msg_sz[ i ] ) return FD_ED25519_HIP_ERR_INVAL;
+  return FD_ED25519_HIP_OK;
+}
+
+unsigned long
+fd_ed25519_hip_private_diag_prep_nmax( fd_ed25519_hip_engine_t * e, int form ) {
+  if( !e ) return 0UL;
+  /* what the dsm form that consumes the arrays admits */
+  switch( form ) {
+  case FD_ED25519_DIAG_PREP_WIDE:   return fd_ed25519_hip_private_diag_dsm_nmax( e, FD_ED25519_DIAG_DSM_WIDE );
+  case FD_ED25519_DIAG_PREP_FUSED1: return fd_ed25519_hip_private_diag_dsm_nmax( e, FD_ED25519_DIAG_DSM_QUAD );
+  case FD_ED25519_DIAG_PREP_FUSED2: return fd_ed25519_hip_private_diag_dsm_nmax( e, FD_ED25519_DIAG_DSM_OCT );
+  case FD_ED25519_DIAG_PREP_R16:
+  case FD_ED25519_DIAG_PREP_R16_DECODE: return fd_ed25519_hip_private_diag_dsm_nmax( e, FD_ED25519_DIAG_DSM_R16 );
+  case FD_ED25519_DIAG_PREP_R16_FULL: {   /* verify_chunk's full_in_prep: a lane-table slot per signature */
+    unsigned long m = fd_ed25519_hip_private_diag_dsm_nmax( e, FD_ED25519_DIAG_DSM_R16 );
+    unsigned long room = lane_atab_bytes( e ) / ( fd_ed25519_hip_atab_bytes_per_wave() / 64UL );
+    if( !FD_ED25519_FULL_IN_PREP ) return 0UL;
+    return room<m ? room : m;
+  }
+  default: return 0UL;
+  }
+}
+
+int
+fd_ed25519_hip_private_diag_prep( fd_ed25519_hip_engine_t * e, int form, unsigned long n, unsigned long cap,
+                                  unsigned char const * sigs, unsigned char const * pubs,
+                                  unsigned char const * msgs, unsigned long const * msg_off,
+                                  unsigned int const * msg_sz, unsigned char const * digests,
+                                  uint32_t * k, unsigned char * sflag, unsigned char * hflag, unsigned char * pflag,
+                                  int32_t * pts, uint32_t * hs, uint32_t * perm, signed char * out, uint32_t * fix ) {
+  if( !e || !k || !sflag || !hflag || !pflag || !pts || !hs || !perm || !out || !fix ) return FD_ED25519_HIP_ERR_INVAL;
+  int err = fd_ed25519_hip_private_diag_prep_check( form, n, fd_ed25519_hip_private_diag_prep_nmax( e, form ), cap,
+                                                    sigs, pubs, msgs, msg_off, msg_sz, digests );
+  if( err ) {
+    snprintf( fd_ed25519_hip_errbuf, sizeof(fd_ed25519_hip_errbuf), "diag_prep: inputs outside the prep phases' contracts" );
+    return err;
+  }
+  HIPCHK( hipSetDevice( e->device ), "hipSetDevice" );
+  size_t msg_bytes = 0UL;
+  if( !digests ) for( unsigned long i=0UL; i<n; i++ ) {
+    size_t end = (size_t)msg_off[ i ] + msg_sz[ i ];
+    if( end>msg_bytes ) msg_bytes = end;
+  }
+  /* one allocation, every array 256-byte aligned in it: the inputs (0..4:
+     sigs, pubs, msgs or digests, msg_off, msg_sz), the work arrays and the
+     codes (5..13, the pattern), the sort's scratch */
+  enum { NIN = 5, NARR = 15 };
+  size_t sz[ NARR ] = { 64UL*n, 32UL*n, digests ? 64UL*n : msg_bytes + 16UL, 8UL*n, 4UL*n,
+                        8UL*4UL*cap, cap, cap, 2UL*cap, 2UL*20UL*4UL*cap, 19UL*4UL*cap, 4UL*cap, cap, 8UL + 4UL*cap,
+                        2UL*FD_ED25519_SORT_BUCKETS*4UL };
+  size_t off[ NARR + 1 ], total = 0UL;
+  for( int i=0; i<NARR; i++ ) { off[ i ] = total; total += ( sz[ i ] + 255UL ) & ~(size_t)255UL; }
+  off[ NARR ] = total;
+  uint8_t * d = NULL;
+  hipError_t he = hipMalloc( (void **)&d, total );
+  if( he==hipSuccess ) he = hipMemsetAsync( d, 0, off[ NIN ], e->stream );
+  if( he==hipSuccess ) he = hipMemsetAsync( d + off[ NIN ], FD_ED25519_DIAG_DSM_UNWRITTEN, total - off[ NIN ], e->stream );
+  void const * src[ NIN ] = { sigs, pubs, digests ? digests : msgs, digests ? NULL : msg_off, digests ? NULL : msg_sz };
+  size_t       cnt[ NIN ] = { sz[ 0 ], sz[ 1 ], digests ? sz[ 2 ] : msg_bytes, sz[ 3 ], sz[ 4 ] };
+  for( int i=0; i<NIN && he==hipSuccess; i++ )
+    if( src[ i ] && cnt[ i ] ) he = hipMemcpyAsync( d + off[ i ], src[ i ], cnt[ i ], hipMemcpyHostToDevice, e->stream );
+  if( he==hipSuccess ) {
+    fd_ed25519_verify_params_t p;
+    memset( &p, 0, sizeof(p) );
+    params_tables( e, &p );
+    p.cap = cap; p.n = n; p.base = 0UL;
+    p.sigs = d + off[ 0 ]; p.pubs = d + off[ 1 ];
+    if( digests ) p.digests = d + off[ 2 ];
+    else { p.msgs = d + off[ 2 ]; p.msg_off = (uint64_t const *)( d + off[ 3 ] ); p.msg_sz = (uint32_t const *)( d + off[ 4 ] ); }
+    p.k = (uint32_t *)( d + off[ 5 ] ); p.sflag = d + off[ 6 ]; p.hflag = d + off[ 7 ]; p.pflag = d + off[ 8 ];
+    p.pts = (int32_t *)( d + off[ 9 ] ); p.hs = (uint32_t *)( d + off[ 10 ] );
+    p.out = (int8_t *)( d + off[ 12 ] );
+    p.fix_cnt = (uint32_t *)( d + off[ 13 ] ); p.work_ctr = p.fix_cnt + 1; p.fix_list = p.fix_cnt + 2;
+    p.hist = (uint32_t *)( d + off[ 14 ] );
+    p.atab = e->lane[0].d_atab;
+    /* verify_chunk's choices, per form */
+    p.small = form>=FD_ED25519_DIAG_PREP_R16 ? 3 : form;
+    p.full_in_prep = form==FD_ED25519_DIAG_PREP_R16_FULL;
+    p.hs_host = form==FD_ED25519_DIAG_PREP_R16_DECODE;
+    p.perm = ( p.small || p.digests ) ? NULL : (uint32_t *)( d + off[ 11 ] );
+    if( p.perm ) {
+      /* hash_kernel takes perm's entries as indices, and an entry the sort
+         did not write would be the fill: the sort is tried first over a perm
+         of zeros (every entry a valid index whatever the sort does), read
+         back and held to be a permutation; only then the launch proper, on
+         the refilled temporaries */
+      uint32_t * hp = (uint32_t *)malloc( 4UL*n );
+      unsigned char * seen = (unsigned char *)calloc( n, 1UL );
+      if( !hp || !seen ) { free( hp ); free( seen ); hipFree( d ); return FD_ED25519_HIP_ERR_NOMEM; }
+      he = hipMemsetAsync( p.perm, 0, 4UL*cap, e->stream );
+      if( he==hipSuccess ) he = (hipError_t)fd_ed25519_hip_launch_phase( &p, FD_ED25519_PHASE_HASH, e->dsm_grid, e->stream );
+      if( he==hipSuccess ) he = hipMemcpyAsync( hp, p.perm, 4UL*n, hipMemcpyDeviceToHost, e->stream );
+      hipError_t pe = hipStreamSynchronize( e->stream );
+      if( he==hipSuccess ) he = pe;
+      int bad = 0;
+      for( unsigned long j=0UL; j<n && he==hipSuccess && !bad; j++ ) {
+        if( hp[ j ]>=n || seen[ hp[ j ] ] ) bad = 1; else seen[ hp[ j ] ] = 1;
+      }
+      free( hp ); free( seen );
+      if( bad ) {
+        hipFree( d );
+        snprintf( fd_ed25519_hip_errbuf, sizeof(fd_ed25519_hip_errbuf), "diag_prep: the sort left perm not a permutation of 0..n-1" );
+        return FD_ED25519_HIP_ERR_INVAL;
+      }
+      if( he==hipSuccess ) he = hipMemsetAsync( d + off[ NIN ], FD_ED25519_DIAG_DSM_UNWRITTEN, off[ NARR - 1 ] - off[ NIN ], e->stream );
+    }
+    static int const phase[ 3 ] = { FD_ED25519_PHASE_HASH, FD_ED25519_PHASE_SCALAR, FD_ED25519_PHASE_DECODE };
+    for( int i=0; i<3 && he==hipSuccess; i++ )
+      he = (hipError_t)fd_ed25519_hip_launch_phase( &p, phase[ i ], e->dsm_grid, e->stream );
+  }
+  void * dst[ 9 ] = { k, sflag, hflag, pflag, pts, hs, perm, out, fix };
+  for( int i=0; i<9 && he==hipSuccess; i++ )
+    he = hipMemcpyAsync( dst[ i ], d + off[ NIN + i ], sz[ NIN + i ], hipMemcpyDeviceToHost, e->stream );
+  hipError_t se = hipStreamSynchronize( e->stream );
+  if( he==hipSuccess ) he = se;
+  hipFree( d );
+  if( he!=hipSuccess ) return hip_fail( he, "diag_prep" );
+  return FD_ED25519_HIP_OK;
+}
+
 int
 fd_ed25519_hip_verify_digests_dev( fd_ed25519_hip_engine_t * e, unsigned long n, unsigned char const * digests,
                                    unsigned char const * sigs, unsigned char const * pubs, signed char * out,

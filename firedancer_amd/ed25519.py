@@ -89,6 +89,11 @@ _lib.fd_ed25519_hip_private_diag_dsm.argtypes = [ctypes.c_void_p, ctypes.c_int, 
 _lib.fd_ed25519_hip_private_diag_dsm_nmax.argtypes = [ctypes.c_void_p, ctypes.c_int]
 _lib.fd_ed25519_hip_private_diag_dsm_nmax.restype = ctypes.c_ulong
 _lib.fd_ed25519_hip_private_diag_dsm_check.argtypes = [ctypes.c_int, ctypes.c_ulong, ctypes.c_ulong, ctypes.c_int] + [_u8p] * 7
+_lib.fd_ed25519_hip_private_diag_prep.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_ulong, ctypes.c_ulong] + [_u8p] * 15
+_lib.fd_ed25519_hip_private_diag_prep_nmax.argtypes = [ctypes.c_void_p, ctypes.c_int]
+_lib.fd_ed25519_hip_private_diag_prep_nmax.restype = ctypes.c_ulong
+_lib.fd_ed25519_hip_private_diag_prep_check.argtypes = [ctypes.c_int, ctypes.c_ulong, ctypes.c_ulong, ctypes.c_ulong] + [_u8p] * 6
+_lib.fd_ed25519_hip_verify_digests_dev.argtypes = [ctypes.c_void_p, ctypes.c_ulong] + [_u8p] * 5
 _lib.fd_ed25519_hip_strerror.argtypes = [ctypes.c_int]
 _lib.fd_ed25519_hip_strerror.restype = ctypes.c_char_p
 
@@ -625,6 +630,65 @@ class Engine:
     def diag_dsm_nmax(self, form):
         """the most signatures diag_dsm takes in that form on this engine"""
         return _lib.fd_ed25519_hip_private_diag_dsm_nmax(self._h, int(form))
+
+    def diag_prep(self, form, sigs, pubs, msgs=None, msg_off=None, msg_sz=None, digests=None, cap=None):
+        """Diagnostic: the hash, scalar and decode phases alone on host
+        inputs (fd_ed25519_hip_private_diag_prep,
+        csrc/fd_ed25519_hip_internal.h): form 0 wide, 1 / 2 the fused prep
+        kernel, 3 prep16, 4 its decode blocks only, 5 prep16 running the
+        full-length items; messages (msgs, msg_off, msg_sz) or digests
+        [n][64].  Returns the work arrays as the kernels left them, stride
+        cap (default n), as a dict: k [8][cap], sflag, hflag, pflag [2][cap],
+        pts [40][cap], hs [19][cap], perm, out, fix_cnt, work_ctr, fix_list
+        -- FD_ED25519_DIAG_DSM_UNWRITTEN (0x55) bytes wherever nothing was
+        written.  Inputs outside the contracts raise HipError before
+        anything is launched."""
+        sigs, pubs = _c(sigs, np.uint8).reshape(-1), _c(pubs, np.uint8).reshape(-1)
+        n = len(sigs) // 64
+        cap = n if cap is None else int(cap)
+        assert len(sigs) == 64 * n and len(pubs) == 32 * n
+        if digests is not None:
+            digests = _c(digests, np.uint8).reshape(-1)
+            assert len(digests) == 64 * n
+            msgs = msg_off = msg_sz = None
+        else:
+            msgs = _c(msgs, np.uint8).reshape(-1) if msgs is not None and len(msgs) else np.zeros(1, np.uint8)
+            msg_off, msg_sz = _c(msg_off, np.uint64), _c(msg_sz, np.uint32)
+            assert len(msg_off) == n and len(msg_sz) == n
+        c = max(cap, 1)
+        a = dict(k=np.zeros((8, c), np.uint32), sflag=np.zeros(c, np.uint8), hflag=np.zeros(c, np.uint8),
+                 pflag=np.zeros((2, c), np.uint8), pts=np.zeros((40, c), np.int32), hs=np.zeros((19, c), np.uint32),
+                 perm=np.zeros(c, np.uint32), out=np.zeros(c, np.int8))
+        fix = np.zeros(2 + c, np.uint32)
+        _check(_lib.fd_ed25519_hip_private_diag_prep(self._h, int(form), n, cap, _ptr(sigs), _ptr(pubs), _ptr(msgs),
+                                                     _ptr(msg_off), _ptr(msg_sz), _ptr(digests),
+                                                     *[_ptr(a[f]) for f in ("k", "sflag", "hflag", "pflag", "pts", "hs",
+                                                                            "perm", "out")], _ptr(fix)))
+        a.update(fix_cnt=int(fix[0]), work_ctr=int(fix[1]), fix_list=fix[2:])
+        return a
+
+    def diag_prep_nmax(self, form):
+        """the most signatures diag_prep takes in that form on this engine"""
+        return _lib.fd_ed25519_hip_private_diag_prep_nmax(self._h, int(form))
+
+    def verify_digests_host(self, digests, sigs, pubs):
+        """SoA host batch with the caller's SHA-512(R||A||M) per signature
+        (digests [n][64]) -> int8 codes (synchronous): staged like
+        verify_host, verified by fd_ed25519_hip_verify_digests_dev."""
+        digests, sigs, pubs = (_c(x, np.uint8).reshape(-1) for x in (digests, sigs, pubs))
+        n = len(digests) // 64
+        assert len(digests) == 64 * n and len(sigs) == 64 * n and len(pubs) == 32 * n
+        if n == 0:
+            return np.zeros(0, dtype=np.int8)
+        bufs = [self.alloc(x.nbytes).upload(x) for x in (digests, sigs, pubs)] + [self.alloc(n)]
+        try:
+            _check(_lib.fd_ed25519_hip_verify_digests_dev(self._h, n, bufs[0].ptr, bufs[1].ptr, bufs[2].ptr, bufs[3].ptr,
+                                                          None))
+            self.sync()
+            return bufs[3].download(np.int8, n)
+        finally:
+            for b in bufs:
+                b.free()
 
     def clock_mhz(self):
         return _lib.fd_ed25519_hip_device_clock_mhz(self._h)

@@ -13,13 +13,7 @@ import time
 import numpy as np
 import pytest
 
-P = 2**255 - 19
-D = (-121665 * pow(121666, P - 2, P)) % P
-SQRTM1 = pow(2, (P - 1) // 4, P)
-OFF = [0, 26, 51, 77, 102, 128, 153, 179, 204, 230]
-# the order-8 points' y (fd25519_dsm.h ge_decode)
-Y0 = int.from_bytes(bytes.fromhex("26e8958fc2b227b045c3f489f2ef98f0d5dfac05d3c63339b13802886d53fc05"), "little")
-Y1 = int.from_bytes(bytes.fromhex("c7176a703d4dd84fba3c0b760d10670f2a2053fa2c39ccc64ec7fd7792ac037a"), "little")
+from prep_model import D, OFF, P, Y0, Y1, expected   # the rules restated: shared with the device decodes' tests
 
 
 @pytest.fixture(scope="module")
@@ -29,25 +23,6 @@ def hsdec():
     f.argtypes = [ctypes.c_char_p, ctypes.c_int, ctypes.c_void_p]
     f.restype = ctypes.c_uint
     return f
-
-
-def expected(enc, avx):
-    raw = int.from_bytes(enc, "little")
-    sign = raw >> 255
-    yr = raw & (2**255 - 1)
-    y = yr % P
-    u, v = (y * y - 1) % P, (D * y * y + 1) % P
-    x = u * pow(v, 3, P) * pow(u * pow(v, 7, P), (P - 5) // 8, P) % P
-    vxx = v * x * x % P
-    root, iroot = vxx == u, vxx == (-u) % P
-    if not root:
-        x = x * SQRTM1 % P
-    x0 = x == 0
-    fail = not (root or iroot) or (avx and x0 and sign == 1)
-    if (x & 1) != sign:
-        x = (P - x) % P
-    small = x0 or y == 0 or y == Y0 or y == Y1
-    return (1 if fail else 0) | (2 if small else 0), x, yr
 
 
 def check(f, enc, avx):
