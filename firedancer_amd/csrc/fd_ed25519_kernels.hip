@@ -31,7 +31,13 @@
    persistent dsm grid (dynamically scheduled, 64 items per wave); the base
    tables [0..2^24)B and [0..2^24)[2^144]B (or the compact radix-2^16 pair)
    and [0..2^15]B (full-length form) in HBM, shared by the engines of a
-   device; [0..128]B in LDS for the signing kernels only. */
+   device; [0..128]B in LDS for the signing kernels only.
+
+   The latency forms of step 5 for small chunks, one window loop per lane
+   layout: a quad or two quads per signature (dsm4, dsm8: wave_windows,
+   ge4_dbl4, ge4_add_signed, quad_finish) and the field arithmetic spread
+   over the lanes (dsm16, dsm16s<S>: go_gate, dsm16_windows,
+   dsm16_finish). */
 #include <hip/hip_runtime.h>
 #include "fd25519_dsm.h"
 #include "fd25519_ge4.h"
@@ -280,17 +286,7 @@ FD_DEV void table_store(int4* tab, int e, ge_cached c) {
 __device__ const int4 fd_ident_cached[10] = {{1, 0, 0, 0}, {0, 0, 0, 0}, {0, 0, 1, 0}, {0, 0, 0, 0}, {0, 0, 0, 0},
                                              {2, 0, 0, 0}, {0, 0, 0, 0}, {0, 0, 0, 0}, {0, 0, 0, 0}, {0, 0, 0, 0}};
 
-/* the entry for digit e: [|e|] of the lane's table (IDENT: [1..8] at 0..7,
-   the shared identity for e == 0) */
-template <bool IDENT>
-FD_DEV const int4* tab_entry(const int4* tab, int e) {
-  const int a = e < 0 ? -e : e;
-  if (IDENT) return a == 0 ? fd_ident_cached : tab + (a - 1) * 10;
-  return tab + a * 10;
-}
-
-/* IDENT: [1..8] at entries 0..7, no identity entry */
-template <bool NT, bool IDENT = false>
+template <bool NT>
 FD_DEV void table_build(int4* tab, const fe& x, const fe& y, bool negate) {
   ge_p3 P0;
   fe xn;
@@ -300,12 +296,10 @@ FD_DEV void table_build(int4* tab, const fe& x, const fe& y, bool negate) {
   fe_1(P0.Z);
   fe_mul(P0.T, P0.X, y);
   ge_cached c1, c;
-  if (!IDENT) {
-    c.YplusX = P0.Z; c.YminusX = P0.Z; fe_add(c.Z2, P0.Z, P0.Z); fe_0(c.T2d);  /* identity */
-    atab_store(tab, 0, c);
-  }
+  c.YplusX = P0.Z; c.YminusX = P0.Z; fe_add(c.Z2, P0.Z, P0.Z); fe_0(c.T2d);  /* identity */
+  atab_store(tab, 0, c);
   ge_p3_to_cached(c1, P0);
-  table_store<NT>(tab, IDENT ? 0 : 1, c1);
+  table_store<NT>(tab, 1, c1);
   /* P0 is affine: the multiples by mixed additions (3 multiplications) */
   ge_precomp pre;
   pre.yplusx = c1.YplusX; pre.yminusx = c1.YminusX; pre.xy2d = c1.T2d;
@@ -316,7 +310,7 @@ FD_DEV void table_build(int4* tab, const fe& x, const fe& y, bool negate) {
     ge_madd(sum, cur, pre);
     ge_p1p1_to_p3_uxyt(cur, sum);   /* Z centered: the next mixed addition doubles it */
     ge_p3_to_cached<true>(c, cur);
-    table_store<NT>(tab, IDENT ? e - 1 : e, c);
+    table_store<NT>(tab, e, c);
   }
 }
 
@@ -401,9 +395,6 @@ FD_DEV bool half_pair_ok(const uint32_t (&k)[8], const uint32_t (&c)[FD_HALF_TW]
    items and a bit of |d| above bit 0 for another 1/8, after the search and
    before the check, so that the check -- not luck -- keeps the verdicts
    bit-exact (tests/test_gpu_halfcheck.py). */
-#ifndef FD_ED25519_AB_LDS_BASE
-#define FD_ED25519_AB_LDS_BASE 0
-#endif
 #ifndef FD_ED25519_HALF_FAULT
 #define FD_ED25519_HALF_FAULT 0
 #endif
@@ -546,6 +537,23 @@ __global__ void __launch_bounds__(192) fd_ed25519_prep_kernel(fd_ed25519_verify_
 FD_DEV void load_hs(uint32_t (&x)[5], const fd_ed25519_verify_params_t& p, int row, int words, uint64_t j) {
 #pragma unroll
   for (int w = 0; w < 5; w++) x[w] = w < words ? p.hs[(uint64_t)(row + w) * p.cap + j] : 0u;
+}
+
+/* The wave's count of signed BITS-bit windows (2 or 4) for c and |d|, from
+   this lane's |d|: a lane needs |d| < 2^(BITS W - 1).  66 / 33 windows
+   unless a lane of the wave has |d| >= 2^131; then one more for each
+   longer length some lane needs (a ballot per length), up to
+   FD_HALF_DBITS_MAX bits: the same W in every lane of the wave.  dsm4 and
+   dsm8 call it; dsm_half_one has the 2-bit count written out (see there). */
+template <int BITS>
+FD_DEV int wave_windows(const uint32_t (&d)[5]) {
+  static_assert(BITS == 2 || BITS == 4, "2-bit or 4-bit windows");
+  constexpr int W0 = 132 / BITS;
+  int W = W0;
+  const int wl = (fd_half_bitlen<5>(d) + BITS) >> (BITS / 2);
+#pragma unroll
+  for (int w = W0 + 1; w <= (FD_HALF_DBITS_MAX + BITS) / BITS; w++) W += __ballot(wl >= w) != 0ull;
+  return W;
 }
 
 /* base digits of s_lo and s_hi in radix 2^BW: digit m sits at bits BW m,
@@ -717,7 +725,10 @@ FD_DEV int dsm_half_one(const fd_ed25519_verify_params_t& p, uint64_t j, int4* t
   {
     uint32_t x[5], t[5];
     load_hs(x, p, 5, 5, j);
-    /* windows this lane needs: |d| < 2^(2W-1); the wave takes the max */
+    /* wave_windows<2>(x), written out: through the helper the compiler
+       orders this kernel's products differently (23,376 -> 23,373
+       instructions, profiles/dsm_forms_refactor_ab.txt), and the throughput
+       kernel stays instruction-identical across refactors */
     const int wl = (fd_half_bitlen<5>(x) + 2) >> 1;
 #pragma unroll
     for (int w = 67; w <= (FD_HALF_DBITS_MAX + 2) / 2; w++) W += __ballot(wl >= w) != 0ull;
@@ -783,90 +794,6 @@ FD_DEV int dsm_half_one(const fd_ed25519_verify_params_t& p, uint64_t j, int4* t
   if (code == FD_PENDING) code = ident ? FD_ED25519_SUCCESS : FD_ED25519_ERR_MSG;
   return code;
 }
-
-#if FD_ED25519_AB_LDS_BASE
-/* A/B build only ("tables staged in LDS"): the base
-   tables in LDS.  2 x 256 entries x 128 B = 64 KiB per block, i.e. radix
-   2^8: s' = s_lo + 2^144 s_hi is re-split at 2^136 into 17 + 15 unsigned
-   8-bit digits at windows 32, 30, .., 0 and 28, .., 0 -- 32 mixed
-   additions from LDS against 11 from the 2 x 2 GiB HBM tables.  Same
-   lane tables, doublings and identity test as dsm_half_one. */
-FD_DEV int dsm_half_one_lds(const fd_ed25519_verify_params_t& p, uint64_t j, int4* tabA, int4* tabR,
-                            const int4* s_lo8, const int4* s_hi8) {
-  int code = precheck(p, j);
-  const uint32_t hf = p.hflag[j];
-  {
-    fe x, y;
-    load_pt(x, y, p, 0, j);
-    table_build<true, true>(tabA, x, y, true);
-    load_pt(x, y, p, 1, j);
-    table_build<true, true>(tabR, x, y, !(hf & FD_HF_DNEG));
-  }
-  uint32_t cd[5], dd[5], ld[5], hd[5];
-  int W = 33;
-  {
-    uint32_t x[5], t[5], sl[5], sh[5];
-    load_hs(x, p, 5, 5, j);
-    const int wl = (fd_half_bitlen<5>(x) + 4) >> 2;
-#pragma unroll
-    for (int w = 34; w <= (FD_HALF_DBITS_MAX + 4) / 4; w++) W += __ballot(wl >= w) != 0ull;
-    const int shv = 160 - 4 * W;
-    shl160v(t, x, shv); recode160<4>(dd, t);
-    load_hs(x, p, 0, 5, j);  shl160v(t, x, shv); recode160<4>(cd, t);
-    load_hs(sl, p, 10, 5, j);
-    load_hs(sh, p, 15, 4, j);
-    static_assert(FD_ED25519_BTABW_SHIFT - FD_ED25519_BTAB8_SHIFT == 8, "re-split of s' by one byte");
-    uint32_t lo[5] = {sl[0], sl[1], sl[2], sl[3], sl[4] & 0xffu};
-    uint32_t hi[5] = {(sl[4] >> 8) | (sh[0] << 8), (sh[0] >> 24) | (sh[1] << 8), (sh[1] >> 24) | (sh[2] << 8),
-                      (sh[2] >> 24) | (sh[3] << 8), sh[3] >> 24};
-    shl160<160 - 17 * 8>(ld, lo);
-    shl160<160 - 15 * 8>(hd, hi);
-  }
-  ge_p3 P;
-  ge_p3_0(P);
-  ge_p1p1 Rt;
-  ge_p2 Q;
-#pragma clang loop unroll(disable)
-  for (int it = W - 1; it >= 0; it--) {
-    int ea = pop160<4>(cd), er = pop160<4>(dd);
-    if (it == W - 1) { ea &= 15; er &= 15; }
-    ge_cached ca, cr;
-    const bool blo = it <= 32 && !(it & 1), bhi = it <= 28 && !(it & 1);
-    ge_precomp b1, b2;
-    atab_load(ca, tab_entry<true>(tabA, ea), 0);
-    if (it != W - 1) {
-#pragma clang loop unroll(disable)
-      for (int dbl = 0; dbl < 4; dbl++) {
-        ge_p2_dbl(Rt, Q);
-        if (dbl < 3) ge_p1p1_to_p2(Q, Rt);
-      }
-      ge_p1p1_to_p3_u(P, Rt);
-    }
-    atab_load(cr, tab_entry<true>(tabR, er), 0);
-    ge_cached_cneg(ca, ea < 0);
-    ge_add<true>(Rt, P, ca);
-    ge_p1p1_to_p3_u(P, Rt);
-    if (blo) btab16_load(b1, s_lo8, (int)pop160u<8>(ld));
-    if (bhi) btab16_load(b2, s_hi8, (int)pop160u<8>(hd));
-    ge_cached_cneg(cr, er < 0);
-    ge_add<true>(Rt, P, cr);
-    if (blo) {
-      ge_p1p1_to_p3_uxyt(P, Rt);
-      ge_madd(Rt, P, b1);
-    }
-    if (bhi) {
-      ge_p1p1_to_p3_uxyt(P, Rt);
-      ge_madd(Rt, P, b2);
-    }
-    ge_p1p1_to_p2(Q, Rt);
-  }
-  fe t;
-  fe_sub(t, Q.Y, Q.Z);
-  const bool ident = fe_iszero(Q.X) && fe_iszero(t);
-  if (code == FD_PENDING) code = ident ? FD_ED25519_SUCCESS : FD_ED25519_ERR_MSG;
-  return code;
-}
-#endif
 
 /* The reference's own form, for the few signatures whose k has no
    half-size pair: R' = [k](-A) + [S]B with k in radix 16 (252 doublings,
@@ -948,17 +875,6 @@ fd_ed25519_dsm_kernel(fd_ed25519_verify_params_t p) {
   int4* tabA = reinterpret_cast<int4*>(static_cast<char*>(p.atab) + wave * FD_ED25519_ATAB_BYTES_PER_WAVE) +
                lane * (2 * FD_ED25519_ATAB_STRIDE * 10);
   /* a lane's space is two 8-entry tables: the joint table's 11 entries, or the full-length form's 9 */
-#if FD_ED25519_AB_LDS_BASE
-  int4* tabR = tabA + FD_ED25519_ATAB_STRIDE * 10;
-  __shared__ int4 s_b8[2 * 256 * (FD_ED25519_BTAB16_STRIDE / 4)];
-  {
-    const int4* g_lo = reinterpret_cast<const int4*>(p.btab8_lo);
-    const int4* g_hi = reinterpret_cast<const int4*>(p.btab8_hi);
-    constexpr int N = 256 * (FD_ED25519_BTAB16_STRIDE / 4);
-    for (int i = threadIdx.x; i < N; i += blockDim.x) { s_b8[i] = g_lo[i]; s_b8[N + i] = g_hi[i]; }
-    __syncthreads();
-  }
-#endif
   if (p.small) {
     /* after dsm4: the full-length items only, found by their flag (a
        static stride: the work counter is not reset for small chunks) */
@@ -981,12 +897,7 @@ fd_ed25519_dsm_kernel(fd_ed25519_verify_params_t p) {
       p.out[p.base + j] = (int8_t)dsm_full_one(p, j, tabA);
     } else if (t >= head && t < total) {
       const uint64_t j = t - head;
-#if FD_ED25519_AB_LDS_BASE
-      if (!(p.hflag[j] & FD_HF_FULL))
-        p.out[p.base + j] = (int8_t)dsm_half_one_lds(p, j, tabA, tabR, s_b8, s_b8 + 256 * (FD_ED25519_BTAB16_STRIDE / 4));
-#else
       if (!(p.hflag[j] & FD_HF_FULL)) p.out[p.base + j] = (int8_t)dsm_half_one<BW>(p, j, tabA);
-#endif
     }
   }
 }
@@ -1056,6 +967,37 @@ FD_DEV void table4_build(int4* tab, const fe& x, const fe& y, bool negate, const
   }
 }
 
+/* a window's four doublings */
+FD_DEV void ge4_dbl4(fe& P, const qmask_t& m) {
+  fe Rt;
+#pragma clang loop unroll(disable)
+  for (int dbl = 0; dbl < 4; dbl++) {
+    ge4_dbl(Rt, P, m);
+    ge4_to_p3(P, Rt);
+  }
+}
+
+/* P += c, or P -= c (neg) as -((-P) + c), c a qc table entry */
+FD_DEV void ge4_add_signed(fe& P, const fe& c, bool neg, const qmask_t& m) {
+  fe Rt;
+  ge4_cneg(P, m.l03, neg);
+  ge4_add(Rt, P, c, m);
+  ge4_cneg(Rt, m.l0, neg);
+  ge4_to_p3(P, Rt);
+}
+
+/* identity: X == 0 and Y == Z (on lane 0 of the quad), then the
+   signature's code, stored by the lanes with `store` set */
+FD_DEV void quad_finish(const fd_ed25519_verify_params_t& p, uint64_t j, const fe& P, int code, bool store) {
+  fe y1, z1, t;
+  fe_qp<FD_QP(1, 1, 1, 1)>(y1, P);
+  fe_qp<FD_QP(2, 2, 2, 2)>(z1, P);
+  fe_sub(t, y1, z1);
+  const bool ident = fe_iszero(P) && fe_iszero(t);
+  if (code == FD_PENDING) code = ident ? FD_ED25519_SUCCESS : FD_ED25519_ERR_MSG;
+  if (store) p.out[p.base + j] = (int8_t)code;
+}
+
 template <int BW>
 __global__ void __launch_bounds__(256) fd_ed25519_dsm4_kernel(fd_ed25519_verify_params_t p) {
   const uint64_t gid = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -1075,13 +1017,11 @@ __global__ void __launch_bounds__(256) fd_ed25519_dsm4_kernel(fd_ed25519_verify_
     table4_build(tabR, x, y, !(hf & FD_HF_DNEG), m);
   }
   uint32_t cd[5], dd[5], ld[5], hd[5];
-  int W = 33;
+  int W;
   {
     uint32_t x[5], t[5];
     load_hs(x, p, 5, 5, j);
-    const int wl = (fd_half_bitlen<5>(x) + 4) >> 2;
-#pragma unroll
-    for (int w = 34; w <= (FD_HALF_DBITS_MAX + 4) / 4; w++) W += __ballot(wl >= w) != 0ull;
+    W = wave_windows<4>(x);
     const int sh = 160 - 4 * W;
     shl160v(t, x, sh); recode160<4>(dd, t);
     load_hs(x, p, 0, 5, j);  shl160v(t, x, sh); recode160<4>(cd, t);
@@ -1098,24 +1038,12 @@ __global__ void __launch_bounds__(256) fd_ed25519_dsm4_kernel(fd_ed25519_verify_
     const bool blo = fd_bw<BW>::lo_at(it), bhi = fd_bw<BW>::hi_at(it);
     fe ca, cr, b1, b2;
     tab4_load(ca, tabA, ea < 0 ? -ea : ea);
-    if (it != W - 1) {
-#pragma clang loop unroll(disable)
-      for (int dbl = 0; dbl < 4; dbl++) {
-        ge4_dbl(Rt, P, m);
-        ge4_to_p3(P, Rt);
-      }
-    }
+    if (it != W - 1) ge4_dbl4(P, m);
     tab4_load(cr, tabR, er < 0 ? -er : er);
-    ge4_cneg(P, m.l03, ea < 0);
-    ge4_add(Rt, P, ca, m);
-    ge4_cneg(Rt, m.l0, ea < 0);
-    ge4_to_p3(P, Rt);
+    ge4_add_signed(P, ca, ea < 0, m);
     if (blo) btab4_load(b1, p.btab_lo, (int)pop160u<BW>(ld), m);
     if (bhi) btab4_load(b2, p.btab_hi, (int)pop160u<BW>(hd), m);
-    ge4_cneg(P, m.l03, er < 0);
-    ge4_add(Rt, P, cr, m);
-    ge4_cneg(Rt, m.l0, er < 0);
-    ge4_to_p3(P, Rt);
+    ge4_add_signed(P, cr, er < 0, m);
     if (blo) {
       ge4_add(Rt, P, b1, m);
       ge4_to_p3(P, Rt);
@@ -1125,14 +1053,7 @@ __global__ void __launch_bounds__(256) fd_ed25519_dsm4_kernel(fd_ed25519_verify_
       ge4_to_p3(P, Rt);
     }
   }
-  /* identity: X == 0 and Y == Z (on lane 0) */
-  fe y1, z1, t;
-  fe_qp<FD_QP(1, 1, 1, 1)>(y1, P);
-  fe_qp<FD_QP(2, 2, 2, 2)>(z1, P);
-  fe_sub(t, y1, z1);
-  const bool ident = fe_iszero(P) && fe_iszero(t);
-  if (code == FD_PENDING) code = ident ? FD_ED25519_SUCCESS : FD_ED25519_ERR_MSG;
-  if (m.l0) p.out[p.base + j] = (int8_t)code;
+  quad_finish(p, j, P, code, m.l0);
 }
 
 /* dsm8: two quads per signature for the smallest chunks.  The four-scalar
@@ -1162,13 +1083,11 @@ __global__ void __launch_bounds__(256) fd_ed25519_dsm8_kernel(fd_ed25519_verify_
     table4_build(tab, x, y, half ? !(hf & FD_HF_DNEG) : true, m);
   }
   uint32_t sd[5], bd[5];
-  int W = 33;
+  int W;
   {
     uint32_t x[5], t[5];
     load_hs(x, p, 5, 5, j);
-    const int wl = (fd_half_bitlen<5>(x) + 4) >> 2;
-#pragma unroll
-    for (int w = 34; w <= (FD_HALF_DBITS_MAX + 4) / 4; w++) W += __ballot(wl >= w) != 0ull;
+    W = wave_windows<4>(x);
     if (!half) load_hs(x, p, 0, 5, j);
     shl160v(t, x, 160 - 4 * W); recode160<4>(sd, t);
     if (half) {
@@ -1190,18 +1109,9 @@ __global__ void __launch_bounds__(256) fd_ed25519_dsm8_kernel(fd_ed25519_verify_
     const bool badd = half ? fd_bw<BW>::hi_at(it) : fd_bw<BW>::lo_at(it);
     fe ce, b;
     tab4_load(ce, tab, e < 0 ? -e : e);
-    if (it != W - 1) {
-#pragma clang loop unroll(disable)
-      for (int dbl = 0; dbl < 4; dbl++) {
-        ge4_dbl(Rt, P, m);
-        ge4_to_p3(P, Rt);
-      }
-    }
+    if (it != W - 1) ge4_dbl4(P, m);
     if (badd) btab4_load(b, btab, (int)pop160u<BW>(bd), m);
-    ge4_cneg(P, m.l03, e < 0);
-    ge4_add(Rt, P, ce, m);
-    ge4_cneg(Rt, m.l0, e < 0);
-    ge4_to_p3(P, Rt);
+    ge4_add_signed(P, ce, e < 0, m);
     if (badd) {
       ge4_add(Rt, P, b, m);
       ge4_to_p3(P, Rt);
@@ -1214,14 +1124,7 @@ __global__ void __launch_bounds__(256) fd_ed25519_dsm8_kernel(fd_ed25519_verify_
   for (int i = 0; i < 10; i++) qs.v[i] = __shfl_down(q.v[i], 4);
   ge4_add(Rt, P, qs, m);
   ge4_to_p3(P, Rt);
-  /* identity: X == 0 and Y == Z (on lane 0 of quad 0) */
-  fe y1, z1, t;
-  fe_qp<FD_QP(1, 1, 1, 1)>(y1, P);
-  fe_qp<FD_QP(2, 2, 2, 2)>(z1, P);
-  fe_sub(t, y1, z1);
-  const bool ident = fe_iszero(P) && fe_iszero(t);
-  if (code == FD_PENDING) code = ident ? FD_ED25519_SUCCESS : FD_ED25519_ERR_MSG;
-  if (m.l0 && !half) p.out[p.base + j] = (int8_t)code;
+  quad_finish(p, j, P, code, m.l0 && !half);   /* quad 0 holds the sum */
 }
 
 /* ------------------------------------------------------------------------
@@ -1236,7 +1139,8 @@ __global__ void __launch_bounds__(256) fd_ed25519_dsm8_kernel(fd_ed25519_verify_
    a scalar branch.  Base entries are the wide / compact tables' (radix
    2^25.5, converted per lane).  Wave 1 hands its point to wave 0 through
    LDS for the last addition and the identity test.  Same digits, windows,
-   tables, additions and order as dsm8. */
+   tables, additions and order as dsm8.  The gate, the window loop and the
+   end (go_gate, dsm16_windows, dsm16_finish) are dsm16s<S>'s too. */
 #include "fd25519_r16.h"
 
 /* base entry e's coordinate for this lane's row, fetched (btab16_fetch,
@@ -1276,16 +1180,81 @@ FD_DEV uint32_t wait_go(const uint32_t* go) {
   return 0u;
 }
 
+/* The launch-ahead gate of the lane-split forms, taken before any hflag /
+   hs load: without params.go the block proceeds; with it (launched ahead
+   of the host's scalars and points) lane 0 polls, one barrier, and the
+   block proceeds on GO_RUN only -- not on CANCEL, not after the spin
+   bound.  Block-uniform. */
+FD_DEV bool go_gate(const fd_ed25519_verify_params_t& p) {
+  if (!p.go) return true;
+  __shared__ uint32_t go;
+  if (threadIdx.x == 0u) go = wait_go(p.go);
+  __syncthreads();
+  return go == FD_ED25519_GO_RUN;
+}
+
+/* The window loop of the lane-split forms: this wave's W signed 4-bit
+   digits (sd, top-aligned, the top one unsigned) against its table, and
+   its base digits (bd, DBITS bits each, the top one first) at the windows
+   base_at(it) names, from the identity.  The base entry is fetched ahead
+   of the window's doublings. */
+template <int DBITS, class BaseAt>
+FD_DEV uint32_t dsm16_windows(uint32_t (&sd)[5], uint32_t (&bd)[5], const uint32_t (&tab)[9], const int32_t* btab,
+                              int W, const r16ctx& k, BaseAt base_at) {
+  const uint32_t one = r16_small(1u, k);
+  uint32_t P = one & k.r12;   /* identity (0, 1, 1, 0) */
+#pragma clang loop unroll(disable)
+  for (int it = W - 1; it >= 0; it--) {
+    int e = pop160<4>(sd);
+    if (it == W - 1) e &= 15;
+    e = __builtin_amdgcn_readfirstlane(e);
+    const bool badd = base_at(it);
+    const uint32_t bdig = (uint32_t)__builtin_amdgcn_readfirstlane((int)(badd ? pop160u<DBITS>(bd) : 0u));
+    const uint32_t ce = table16_at(tab, e < 0 ? -e : e);
+    fe braw;
+    if (badd) braw = btab16_fetch(btab, (int)bdig, k);   /* in flight during the doublings */
+    if (it != W - 1) {
+      P = ge16_dbl2<false, false>(P, k);   /* (X, Y, Z, X) between doublings: T only before an addition */
+      P = ge16_dbl2<true, false>(P, k);
+      P = ge16_dbl2<true, false>(P, k);
+      P = ge16_dbl2<true, true>(P, k);
+    }
+    uint32_t b = 0u;
+    if (badd) b = btab16_r16(braw, k);
+    if (e != 0) {   /* a zero digit (~1 in 16) adds the identity: skipped, the digit is wave-uniform */
+      P = ge16_cneg4(P, k.r03, e < 0, k);
+      P = ge16_add2<true>(P, ce, e < 0, k);
+    }
+    if (badd) P = ge16_add2<true>(P, b, false, k);
+  }
+  return P;
+}
+
+/* The end of the lane-split forms, on wave 0 with the sum P: the identity
+   test, the reference's earlier checks, the code. */
+FD_DEV void dsm16_finish(const fd_ed25519_verify_params_t& p, uint64_t j, uint32_t P, const r16ctx& k) {
+  /* identity: X == 0 (row 0) and Y == Z (row 1: Y + 4p - Z) */
+  const uint32_t z = r16_rp<2, 2, 2, 2>(P, k);
+  const bool zero = r16_iszero(P + ((k.p4 - z) & k.r1));
+  const uint64_t bal = __ballot(zero);
+  const bool ident = (bal & 1ull) && (bal & (1ull << 16));
+  int code = precheck(p, j);   /* S < L, decode failures, small order: the reference's order */
+  if (code == FD_PENDING) code = ident ? FD_ED25519_SUCCESS : FD_ED25519_ERR_MSG;
+  /* Write-code-last invariant: a signature's code is the last thing any
+     kernel of its launch does with that signature; no kernel reads the
+     inputs (or anything else in the drop-in's pinned block) after the code
+     is written.  The drop-in's direct launches return once every code has
+     landed in that block (host/fd_ed25519_hip_engine.c, dropin_run) and the
+     next call restages it; a kernel added after dsm16 that reads the block
+     would break that silently. */
+  if (threadIdx.x == 0u) p.out[p.base + j] = (int8_t)code;
+}
+
 template <int BW>
 __global__ void __launch_bounds__(128) fd_ed25519_dsm16_kernel(fd_ed25519_verify_params_t p) {
   const uint64_t j = blockIdx.x;   /* a block (two waves) per signature: every return below is block-uniform */
   if (j >= p.n) return;
-  if (p.go) {   /* launched ahead of the host's scalars and points */
-    __shared__ uint32_t go;
-    if (threadIdx.x == 0u) go = wait_go(p.go);
-    __syncthreads();
-    if (go != FD_ED25519_GO_RUN) return;
-  }
+  if (!go_gate(p)) return;
   const uint32_t hf = p.hflag[j];
   const int half = (int)(threadIdx.x >> 6);   /* 0: -A and B, 1: -+R and B' */
   /* the scalars loaded first, used after the table build: with host
@@ -1316,54 +1285,16 @@ __global__ void __launch_bounds__(128) fd_ed25519_dsm16_kernel(fd_ed25519_verify
     else      shl160<fd_bw<BW>::LO_SHL>(bd, hb);
   }
   W = __builtin_amdgcn_readfirstlane(W);
-  const int32_t* btab = half ? p.btab_hi : p.btab_lo;
-  const uint32_t one = r16_small(1u, k);
-  uint32_t P = one & k.r12;   /* identity (0, 1, 1, 0) */
-#pragma clang loop unroll(disable)
-  for (int it = W - 1; it >= 0; it--) {
-    int e = pop160<4>(sd);
-    if (it == W - 1) e &= 15;
-    e = __builtin_amdgcn_readfirstlane(e);
-    const bool badd = half ? fd_bw<BW>::hi_at(it) : fd_bw<BW>::lo_at(it);
-    const uint32_t bdig = (uint32_t)__builtin_amdgcn_readfirstlane((int)(badd ? pop160u<BW>(bd) : 0u));
-    const uint32_t ce = table16_at(tab, e < 0 ? -e : e);
-    fe braw;
-    if (badd) braw = btab16_fetch(btab, (int)bdig, k);   /* in flight during the doublings */
-    if (it != W - 1) {
-      P = ge16_dbl2<false, false>(P, k);   /* (X, Y, Z, X) between doublings: T only before an addition */
-      P = ge16_dbl2<true, false>(P, k);
-      P = ge16_dbl2<true, false>(P, k);
-      P = ge16_dbl2<true, true>(P, k);
-    }
-    uint32_t b = 0u;
-    if (badd) b = btab16_r16(braw, k);
-    if (e != 0) {   /* a zero digit (~1 in 16) adds the identity: skipped, the digit is wave-uniform */
-      P = ge16_cneg4(P, k.r03, e < 0, k);
-      P = ge16_add2<true>(P, ce, e < 0, k);
-    }
-    if (badd) P = ge16_add2<true>(P, b, false, k);
-  }
+  uint32_t P = dsm16_windows<BW>(sd, bd, tab, half ? p.btab_hi : p.btab_lo, W, k, [half](int it) {
+    return half ? fd_bw<BW>::hi_at(it) : fd_bw<BW>::lo_at(it);
+  });
   /* wave 1's point as an addend of wave 0's */
   __shared__ uint32_t hand[64];
   if (half) hand[threadIdx.x & 63u] = ge16_to_qc(P, d2, k);
   __syncthreads();
   if (half) return;
   P = ge16_add2<true>(P, hand[threadIdx.x], false, k);
-  /* identity: X == 0 (row 0) and Y == Z (row 1: Y + 4p - Z) */
-  const uint32_t z = r16_rp<2, 2, 2, 2>(P, k);
-  const bool zero = r16_iszero(P + ((k.p4 - z) & k.r1));
-  const uint64_t bal = __ballot(zero);
-  const bool ident = (bal & 1ull) && (bal & (1ull << 16));
-  int code = precheck(p, j);   /* S < L, decode failures, small order: the reference's order */
-  if (code == FD_PENDING) code = ident ? FD_ED25519_SUCCESS : FD_ED25519_ERR_MSG;
-  /* Write-code-last invariant: a signature's code is the last thing any
-     kernel of its launch does with that signature; no kernel reads the
-     inputs (or anything else in the drop-in's pinned block) after the code
-     is written.  The drop-in's direct launches return once every code has
-     landed in that block (host/fd_ed25519_hip_engine.c, dropin_run) and the
-     next call restages it; a kernel added after dsm16 that reads the block
-     would break that silently. */
-  if (threadIdx.x == 0u) p.out[p.base + j] = (int8_t)code;
+  dsm16_finish(p, j, P, k);
 }
 
 /* ------------------------------------------------------------------------
@@ -1396,12 +1327,7 @@ __global__ void __launch_bounds__(64 * S) fd_ed25519_dsm16s_kernel(fd_ed25519_ve
   constexpr int NB = (CB + 15) / 16, WMIN = S == 4 ? 17 : 9, SH0 = S == 4 ? 64 : 96;
   const uint64_t j = blockIdx.x;   /* a block (S waves) per signature: every return below is block-uniform */
   if (j >= p.n) return;
-  if (p.go) {
-    __shared__ uint32_t go;
-    if (threadIdx.x == 0u) go = wait_go(p.go);
-    __syncthreads();
-    if (go != FD_ED25519_GO_RUN) return;
-  }
+  if (!go_gate(p)) return;
   const uint32_t hf = p.hflag[j];
   const int q = (int)(threadIdx.x >> 6), side = q / H, part = q % H;
   uint32_t hk[5] = {0u, 0u, 0u, 0u, 0u}, hb[5] = {0u, 0u, 0u, 0u, 0u};
@@ -1447,33 +1373,7 @@ __global__ void __launch_bounds__(64 * S) fd_ed25519_dsm16s_kernel(fd_ed25519_ve
     recode160<4>(sd, t);
     shl160<160 - 16 * NB>(bd, hb);           /* the chunk's 16-bit digits, the top one first */
   }
-  const int32_t* btab = p.btabq[q];
-  const uint32_t one = r16_small(1u, k);
-  uint32_t P = one & k.r12;   /* identity (0, 1, 1, 0) */
-#pragma clang loop unroll(disable)
-  for (int it = W - 1; it >= 0; it--) {
-    int e = pop160<4>(sd);
-    if (it == W - 1) e &= 15;
-    e = __builtin_amdgcn_readfirstlane(e);
-    const bool badd = it < 4 * NB && (it & 3) == 0;
-    const uint32_t bdig = (uint32_t)__builtin_amdgcn_readfirstlane((int)(badd ? pop160u<16>(bd) : 0u));
-    const uint32_t ce = table16_at(tab, e < 0 ? -e : e);
-    fe braw;
-    if (badd) braw = btab16_fetch(btab, (int)bdig, k);
-    if (it != W - 1) {
-      P = ge16_dbl2<false, false>(P, k);
-      P = ge16_dbl2<true, false>(P, k);
-      P = ge16_dbl2<true, false>(P, k);
-      P = ge16_dbl2<true, true>(P, k);
-    }
-    uint32_t b = 0u;
-    if (badd) b = btab16_r16(braw, k);
-    if (e != 0) {
-      P = ge16_cneg4(P, k.r03, e < 0, k);
-      P = ge16_add2<true>(P, ce, e < 0, k);
-    }
-    if (badd) P = ge16_add2<true>(P, b, false, k);
-  }
+  uint32_t P = dsm16_windows<16>(sd, bd, tab, p.btabq[q], W, k, [](int it) { return it < 4 * NB && (it & 3) == 0; });
   /* the waves' points summed by halves: waves [h, 2h) hand theirs to
      [0, h); every wave reaches every barrier */
   __shared__ uint32_t hand[S / 2][64];
@@ -1485,14 +1385,7 @@ __global__ void __launch_bounds__(64 * S) fd_ed25519_dsm16s_kernel(fd_ed25519_ve
     __syncthreads();
   }
   if (q) return;
-  const uint32_t z = r16_rp<2, 2, 2, 2>(P, k);
-  const bool zero = r16_iszero(P + ((k.p4 - z) & k.r1));
-  const uint64_t bal = __ballot(zero);
-  const bool ident = (bal & 1ull) && (bal & (1ull << 16));
-  int code = precheck(p, j);
-  if (code == FD_PENDING) code = ident ? FD_ED25519_SUCCESS : FD_ED25519_ERR_MSG;
-  /* the code last (dsm16's write-code-last invariant) */
-  if (threadIdx.x == 0u) p.out[p.base + j] = (int8_t)code;
+  dsm16_finish(p, j, P, k);
 }
 
 extern "C" int fd_ed25519_hip_launch_dsm16s(const fd_ed25519_verify_params_t* p, int waves, void* stream) {
@@ -1629,7 +1522,7 @@ FD_DEV void hash16_block(const fd_ed25519_verify_params_t& p, uint64_t* sched) {
     else if (dr.small) code = FD_ED25519_ERR_SIG;
     int4* tabA = reinterpret_cast<int4*>(static_cast<char*>(p.atab) + (j >> 6) * FD_ED25519_ATAB_BYTES_PER_WAVE) +
                  (j & 63u) * (2 * FD_ED25519_ATAB_STRIDE * 10);
-    /* the code last: see the write-code-last invariant at dsm16's end */
+    /* the code last: see the write-code-last invariant in dsm16_finish */
     p.out[p.base + j] = (int8_t)dsm_full_core(p, j, tabA, code, da.x, da.y, dr.x, dr.y);
   }
 #endif
@@ -1881,12 +1774,6 @@ extern "C" int fd_ed25519_hip_launch_gen_btab(int32_t* d_btab, void* stream) {
   return (int)hipGetLastError();
 }
 
-extern "C" int fd_ed25519_hip_launch_gen_btab8(int32_t* d_tab, int base_dbl, void* stream) {
-  hipLaunchKernelGGL(fd_ed25519_gen_btab_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, d_tab, 256,
-                     FD_ED25519_BTAB16_STRIDE, 8, base_dbl);
-  return (int)hipGetLastError();
-}
-
 extern "C" int fd_ed25519_hip_launch_gen_btab16(int32_t* d_btab16, int base_dbl, void* stream) {
   const int entries = FD_ED25519_BTAB16_ENTRIES;
   hipLaunchKernelGGL(fd_ed25519_gen_btab_kernel, dim3((entries + 255) / 256), dim3(256), 0, (hipStream_t)stream,
@@ -1927,6 +1814,13 @@ extern "C" int fd_ed25519_hip_launch_gen_btabw(int32_t* d_tab, int base_dbl, int
                      d_tab, entries, bits, (const int32_t*)base, d_scratch);
   return (int)hipGetLastError();
 }
+
+/* a dsm kernel's instantiation for the wide or the compact base tables */
+#define FD_LAUNCH_BW(kernel, grid, block)                                                        \
+  do {                                                                                           \
+    if (compact) hipLaunchKernelGGL(kernel<FD_ED25519_BTABC_BITS>, grid, dim3(block), 0, st, *p); \
+    else         hipLaunchKernelGGL(kernel<FD_ED25519_BTABW_BITS>, grid, dim3(block), 0, st, *p); \
+  } while (0)
 
 extern "C" int fd_ed25519_hip_launch_phase(const fd_ed25519_verify_params_t* p, int phase, uint32_t grid,
                                            void* stream) {
@@ -1969,45 +1863,38 @@ extern "C" int fd_ed25519_hip_launch_phase(const fd_ed25519_verify_params_t* p, 
                        *p);
     break;
   case FD_ED25519_PHASE_DSM: {
+    const bool compact = p->bw_bits == FD_ED25519_BTABC_BITS;
     if (p->small) {
       /* a quad / two quads / two waves per signature, then the (rare)
          full-length items, found by a scan of the flags -- unless prep16
          ran them (full_in_prep) */
-      const bool compact = p->bw_bits == FD_ED25519_BTABC_BITS;
       const dim3 g8((uint32_t)((8 * p->n + 255) / 256)), g4((uint32_t)((4 * p->n + 255) / 256));
       if (p->small == 3) {
-        const dim3 g16((uint32_t)p->n);
-        if (compact) hipLaunchKernelGGL(fd_ed25519_dsm16_kernel<FD_ED25519_BTABC_BITS>, g16, dim3(128), 0, st, *p);
-        else         hipLaunchKernelGGL(fd_ed25519_dsm16_kernel<FD_ED25519_BTABW_BITS>, g16, dim3(128), 0, st, *p);
+        FD_LAUNCH_BW(fd_ed25519_dsm16_kernel, dim3((uint32_t)p->n), 128);
         if (p->full_in_prep || p->hs_host) break;   /* the full-length items were done in prep16, or there are
                                                        none (host scalars): no scan */
       } else if (p->small == 2) {
-        if (compact) hipLaunchKernelGGL(fd_ed25519_dsm8_kernel<FD_ED25519_BTABC_BITS>, g8, dim3(256), 0, st, *p);
-        else         hipLaunchKernelGGL(fd_ed25519_dsm8_kernel<FD_ED25519_BTABW_BITS>, g8, dim3(256), 0, st, *p);
+        FD_LAUNCH_BW(fd_ed25519_dsm8_kernel, g8, 256);
       } else {
-        if (compact) hipLaunchKernelGGL(fd_ed25519_dsm4_kernel<FD_ED25519_BTABC_BITS>, g4, dim3(256), 0, st, *p);
-        else         hipLaunchKernelGGL(fd_ed25519_dsm4_kernel<FD_ED25519_BTABW_BITS>, g4, dim3(256), 0, st, *p);
+        FD_LAUNCH_BW(fd_ed25519_dsm4_kernel, g4, 256);
       }
       const uint64_t need = (p->n + FD_ED25519_VERIFY_BLOCK - 1) / FD_ED25519_VERIFY_BLOCK;
       const uint32_t g = (uint32_t)(need < grid ? need : grid);
-      if (compact) hipLaunchKernelGGL(fd_ed25519_dsm_kernel<FD_ED25519_BTABC_BITS>, dim3(g), dim3(FD_ED25519_VERIFY_BLOCK), 0, st, *p);
-      else         hipLaunchKernelGGL(fd_ed25519_dsm_kernel<FD_ED25519_BTABW_BITS>, dim3(g), dim3(FD_ED25519_VERIFY_BLOCK), 0, st, *p);
+      FD_LAUNCH_BW(fd_ed25519_dsm_kernel, dim3(g), FD_ED25519_VERIFY_BLOCK);
       break;
     }
     /* one wave more than the chunk needs: the full-length items (counted on
        the device) run in waves of their own, in parallel with the rest */
     const uint64_t need = (p->n + 64 + FD_ED25519_VERIFY_BLOCK - 1) / FD_ED25519_VERIFY_BLOCK;
     const uint32_t g = (uint32_t)(need < grid ? need : grid);
-    if (p->bw_bits == FD_ED25519_BTABC_BITS)
-      hipLaunchKernelGGL(fd_ed25519_dsm_kernel<FD_ED25519_BTABC_BITS>, dim3(g), dim3(FD_ED25519_VERIFY_BLOCK), 0, st, *p);
-    else
-      hipLaunchKernelGGL(fd_ed25519_dsm_kernel<FD_ED25519_BTABW_BITS>, dim3(g), dim3(FD_ED25519_VERIFY_BLOCK), 0, st, *p);
+    FD_LAUNCH_BW(fd_ed25519_dsm_kernel, dim3(g), FD_ED25519_VERIFY_BLOCK);
   } break;
   default:
     return (int)hipErrorInvalidValue;
   }
   return (int)hipGetLastError();
 }
+#undef FD_LAUNCH_BW
 
 extern "C" int fd_ed25519_hip_launch_verify(const fd_ed25519_verify_params_t* p, uint32_t grid, void* stream) {
   for (int ph = 0; ph < FD_ED25519_PHASE_CNT; ph++) {

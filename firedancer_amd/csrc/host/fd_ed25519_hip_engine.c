@@ -56,7 +56,6 @@ struct fd_ed25519_hip_engine {
 
   int32_t *    d_btab;
   int32_t *    d_btab16;     /* [0..2^15]B, the verify kernels' wide B table  */
-  int32_t *    d_btab8[2];   /* A/B build only (FD_ED25519_AB_LDS_BASE): the LDS-staged tables */
   int32_t *    btabw[2];    /* shared per device: [0..2^24)B, [0..2^24)[2^144]B */
   int32_t *    btabs[2][8]; /* shared per device: dsm16s<4>'s and <8>'s compact tables, when acquired */
   /* Pipeline lanes: the per-chunk scratch of a chunk in flight, and the
@@ -319,21 +318,10 @@ stream_set_size( void ) {
 static int
 stream_acquire( int device, hipStream_t const * avoid, int avoid_cnt, hipStream_t * out ) {
   if( device<0 || device>=FD_ED25519_HIP_MAX_DEV ) return FD_ED25519_HIP_ERR_INVAL;
-#ifdef FD_ED25519_HIP_AB_FRESH_STREAMS
-  /* A/B build only (tools/build_variant.sh): a new stream per request, as
-     in round 2 */
-  (void)avoid; (void)avoid_cnt;
-  { hipError_t he = hipStreamCreateWithFlags( out, hipStreamNonBlocking );
-    return he==hipSuccess ? FD_ED25519_HIP_OK : hip_fail( he, "stream" ); }
-#endif
   pthread_mutex_lock( &sset_lock );
   int rc = FD_ED25519_HIP_OK;
   if( !sset[device].cnt ) {
     int n = stream_set_size();
-#ifdef FD_ED25519_HIP_AB_SET_SKIP
-    /* A/B build only: streams created (and never used) before the set */
-    for( int i=0; i<FD_ED25519_HIP_AB_SET_SKIP; i++ ) { hipStream_t t; (void)hipStreamCreateWithFlags( &t, hipStreamNonBlocking ); }
-#endif
     for( int i=0; i<n; i++ ) {
       hipError_t he = hipStreamCreateWithFlags( &sset[device].s[i], hipStreamNonBlocking );
       if( he!=hipSuccess ) {
@@ -364,10 +352,6 @@ stream_acquire( int device, hipStream_t const * avoid, int avoid_cnt, hipStream_
 static void
 stream_release( int device, hipStream_t st ) {
   if( !st || device<0 || device>=FD_ED25519_HIP_MAX_DEV ) return;
-#ifdef FD_ED25519_HIP_AB_FRESH_STREAMS
-  hipStreamDestroy( st );
-  return;
-#endif
   pthread_mutex_lock( &sset_lock );
   for( int i=0; i<sset[device].cnt; i++ )
     if( sset[device].s[i]==st && sset[device].users[i]>0 ) { sset[device].users[i]--; break; }
@@ -385,7 +369,7 @@ engine_free( fd_ed25519_hip_engine_t * e ) {
     if( e->lane[l].stream ) hipStreamSynchronize( e->lane[l].stream );
     if( e->lane[l].side   ) hipStreamSynchronize( e->lane[l].side );
   }
-  hipFree( e->d_btab ); hipFree( e->d_btab16 ); hipFree( e->d_btab8[0] ); hipFree( e->d_btab8[1] );
+  hipFree( e->d_btab ); hipFree( e->d_btab16 );
   for( int l=0; l<2; l++ ) { hipFree( e->lane[l].d_atab ); hipFree( e->lane[l].d_work ); }
   if( e->btabw[0] ) btabw_release( e->device, engine_btab_kind( e ) );
   if( e->btabs[0][0] ) btabs_release( e->device, 4 );
@@ -537,13 +521,6 @@ engine_init( fd_ed25519_hip_engine_t * e, int device, uint64_t max_chunk, int fl
   if( err ) return hip_fail( (hipError_t)err, "gen_btab launch" );
   err = fd_ed25519_hip_launch_gen_btab16( e->d_btab16, 0, e->stream );
   if( err ) return hip_fail( (hipError_t)err, "gen_btab16 launch" );
-#ifdef FD_ED25519_AB_LDS_BASE
-  for( int t=0; t<2; t++ ) {
-    HIPCHK( hipMalloc( (void **)&e->d_btab8[t], sizeof(int32_t) * 256UL * FD_ED25519_BTAB16_STRIDE ), "hipMalloc(btab8)" );
-    err = fd_ed25519_hip_launch_gen_btab8( e->d_btab8[t], t ? FD_ED25519_BTAB8_SHIFT : 0, e->stream );
-    if( err ) return hip_fail( (hipError_t)err, "gen_btab8 launch" );
-  }
-#endif
   HIPCHK( hipStreamSynchronize( e->stream ), "gen_btab" );
   int32_t * tw[2] = { NULL, NULL };
   err = btabw_acquire( e->device, engine_btab_kind( e ), e->stream, tw );
@@ -699,7 +676,6 @@ static void
 params_tables( fd_ed25519_hip_engine_t * e, fd_ed25519_verify_params_t * p ) {
   p->cap = e->max_chunk;
   p->btab = e->d_btab; p->btab16 = e->d_btab16; p->btab_lo = e->btabw[0]; p->btab_hi = e->btabw[1];
-  p->btab8_lo = e->d_btab8[0]; p->btab8_hi = e->d_btab8[1];
   p->bw_bits = engine_btab_kind( e ) ? FD_ED25519_BTABC_BITS : FD_ED25519_BTABW_BITS;
   p->codes_portable = (e->flags & FD_ED25519_HIP_FLAG_CODES_PORTABLE) ? 1 : 0;
   p->half_dbits     = engine_half_dbits( e );

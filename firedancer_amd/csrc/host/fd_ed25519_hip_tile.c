@@ -372,8 +372,7 @@ fd_ed25519_hip_pipe_new( int device, unsigned slot_cnt, unsigned long sig_cap, u
 #define SLOT_ONE_COPY_SLACK (256UL << 10)
 
 typedef struct {
-  unsigned char const * src;   /* host address (page-locked) */
-  unsigned char const * dev;   /* ... as the device sees it  */
+  unsigned char const * dev;   /* the page-locked host address, as the device sees it */
   unsigned char *       dst;
   unsigned long         n;
 } h2d_span_t;
@@ -388,8 +387,7 @@ slot_h2d_spans( pipe_slot_t * s, unsigned long sig_cnt, unsigned long txn_cnt, u
   unsigned long used = 96UL*sig_cnt + 12UL*oc_cnt + 8UL*txn_cnt + msg_bytes;
   unsigned long whole = s->in_msgs + msg_bytes;
   unsigned k = 0U;
-#define SPAN( host, dptr, bytes ) do { sp[ k ].src = (unsigned char const *)(host);                                  \
-                                       sp[ k ].dev = s->h_in_dev + ( (unsigned char const *)(host) - s->h_in );      \
+#define SPAN( host, dptr, bytes ) do { sp[ k ].dev = s->h_in_dev + ( (unsigned char const *)(host) - s->h_in );      \
                                        sp[ k ].dst = (unsigned char *)(dptr); sp[ k ].n = (bytes); k++; } while(0)
   if( whole - used <= SLOT_ONE_COPY_SLACK ) {
     SPAN( s->h_in, s->d_in, whole ? whole : 1UL );
@@ -427,21 +425,18 @@ static int
 slot_h2d( fd_ed25519_hip_pipe_t * pipe, pipe_slot_t * s, hipStream_t st, unsigned long sig_cnt,
           unsigned long txn_cnt, unsigned long msg_bytes ) {
   int ordered = sig_cnt>FD_ED25519_HIP_PIPE_H2D_ORDER_MIN;
-#ifndef FD_ED25519_HIP_AB_POOL_PARALLEL_H2D
   if( ordered && pipe->h2d_tail ) {
     hipError_t we_;
     PF_SUB( pf_sub_wait, we_ = hipStreamWaitEvent( st, pipe->h2d_tail, 0U ) );
     TCHK( we_, "hipStreamWaitEvent(h2d)" );
   }
-#endif
   h2d_span_t sp[ 9 ];
   unsigned k = slot_h2d_spans( s, sig_cnt, txn_cnt, s->ext_src[0] ? 0UL : msg_bytes, sp );
   for( int g=0; g<2 && s->ext_src[g] && s->ext_len[g]; g++ ) {   /* zero-copy payloads */
-    sp[ k ].src = s->ext_src[g]; sp[ k ].dev = s->ext_dev[g]; sp[ k ].n = s->ext_len[g];
+    sp[ k ].dev = s->ext_dev[g]; sp[ k ].n = s->ext_len[g];
     sp[ k ].dst = s->d_msgs + ( g ? STAGE_ALIGN( s->ext_len[0] ) : 0UL );
     k++;
   }
-#ifndef FD_ED25519_HIP_AB_COPY_ENGINES
   for( unsigned i0=0U; i0<k; i0+=FD_ED25519_PULL_SPAN_MAX ) {   /* one launch moves up to 8 spans (9 at most here) */
     fd_ed25519_pull_params_t pp;
     memset( &pp, 0, sizeof(pp) );
@@ -451,10 +446,6 @@ slot_h2d( fd_ed25519_hip_pipe_t * pipe, pipe_slot_t * s, hipStream_t st, unsigne
     int le = fd_ed25519_hip_launch_pull( &pp, st );
     if( le ) return tile_fail( "H2D pull launch", (hipError_t)le );
   }
-#else
-  for( unsigned i=0U; i<k; i++ )
-    TCHK( hipMemcpyAsync( sp[ i ].dst, sp[ i ].src, sp[ i ].n, hipMemcpyHostToDevice, st ), "H2D batch" );
-#endif
   if( ordered ) {
     TCHK( hipEventRecord( s->ev_h2d, st ), "hipEventRecord(h2d)" );
     pipe->h2d_tail = s->ev_h2d;
@@ -472,15 +463,11 @@ static int
 slot_d2h( pipe_slot_t * s, hipStream_t st, unsigned long sig_cnt, unsigned long txn_cnt, int trailers ) {
   unsigned long n = trailers ? s->out_trl + 64UL*txn_cnt : (txn_cnt ? s->pub.sig_cap + txn_cnt : sig_cnt);
   if( !n ) return FD_ED25519_HIP_OK;
-#ifndef FD_ED25519_HIP_AB_COPY_ENGINES
   fd_ed25519_pull_params_t pp;
   memset( &pp, 0, sizeof(pp) );
   pp.src[0] = (unsigned char const *)s->d_outb; pp.dst[0] = s->h_outb_dev; pp.n[0] = n; pp.cnt = 1U;
   int le = fd_ed25519_hip_launch_pull( &pp, st );
   if( le ) return tile_fail( "D2H push launch", (hipError_t)le );
-#else
-  TCHK( hipMemcpyAsync( s->h_outb, s->d_outb, n, hipMemcpyDeviceToHost, st ), "D2H codes" );
-#endif
   return FD_ED25519_HIP_OK;
 }
 
@@ -2634,7 +2621,6 @@ pool_enqueue( pool_job_t * j, pool_slot_t * s, unsigned long b ) {
   unsigned long lo, hi, bytes;
   batch_span( j, i0, i1, &lo, &hi, &bytes );
   unsigned char const * dmsgs;
-#ifndef FD_ED25519_HIP_AB_POOL_PARALLEL_H2D
   /* One batch crosses the link at a time: this batch's copies start once
      the previous batch's are done (its kernels still overlap them).  Two
      batches copying at once split the link between two DMA streams and
@@ -2642,7 +2628,6 @@ pool_enqueue( pool_job_t * j, pool_slot_t * s, unsigned long b ) {
      with 3 slots, 69M/s with 2, depending on where the slots' streams
      land on the device's hardware queues). */
   if( j->h2d_tail ) TCHK( hipStreamWaitEvent( st, j->h2d_tail, 0U ), "hipStreamWaitEvent(h2d)" );
-#endif
   if( j->direct_in && span_direct( pl, hi-lo, bytes ) ) {
     if( hi>lo ) TCHK( hipMemcpyAsync( s->d_msgs, j->msgs + lo, hi-lo, hipMemcpyHostToDevice, st ), "H2D msgs" );
     TCHK( hipMemcpyAsync( s->d_off,  j->msg_off + i0, 8UL*cnt,  hipMemcpyHostToDevice, st ), "H2D off"  );
