@@ -2,7 +2,7 @@
    decide for the CRDS values of a gossip pull response or push message
    before they call fd_ed25519_verify, restated once and compiled three ways:
    into the device stage kernel (fd_ed25519_crds.hip, hipcc), into the host
-   library (host/fd_ed25519_hip_engine.c, gcc: fd_ed25519_hip_crds_count,
+   library (host/fd_ed25519_hip_fronts.c, gcc: fd_ed25519_hip_crds_count,
    _crds_plan) and into the hostile input test's stand-alone program
    (tests/crds_walk_main.c, gcc with sanitizers).  Include after
    fd_txn_parse_core.h (fd_txn_core_cu16, fd_txn_core_parse_prefix).  The

@@ -14,7 +14,7 @@
             signature and key, empty message) whose verify code nothing
             reads.
      verify the engine's phases over the n_val slots
-            (host/fd_ed25519_hip_engine.c)
+            (host/fd_ed25519_hip_fronts.c)
      finish per value the stage's code, else ERR_SIGNATURE for a verify code
             other than success, else 0, and the optional verify codes; per
             packet its code

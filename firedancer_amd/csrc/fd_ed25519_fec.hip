@@ -12,7 +12,7 @@
               shred's proof; the root goes into the workspace as the 32-byte
               message of the set's signature
      sign     fd_ed25519_sign_kernel (fd_ed25519_gen.hip) over the n_set
-              roots (host/fd_ed25519_hip_engine.c launches it)
+              roots (host/fd_ed25519_hip_fronts.c launches it)
      scatter  one lane per shred copies its set's signature into s[0..64)
 
    The write hazard.  Shreds may start at any byte and 1203 is odd, so shreds

@@ -1,5 +1,5 @@
 /* fd_ed25519_hip_internal.h -- contract between the plain-C host runtime
-   (host/fd_ed25519_hip_engine.c) and the HIP kernel shim
+   (host/fd_ed25519_hip_*.c) and the HIP kernel shim
    (fd_ed25519_kernels.hip).  Only plain pointers and sizes cross it. */
 #ifndef FD_ED25519_HIP_INTERNAL_H
 #define FD_ED25519_HIP_INTERNAL_H

@@ -1244,7 +1244,7 @@ FD_DEV void dsm16_finish(const fd_ed25519_verify_params_t& p, uint64_t j, uint32
      kernel of its launch does with that signature; no kernel reads the
      inputs (or anything else in the drop-in's pinned block) after the code
      is written.  The drop-in's direct launches return once every code has
-     landed in that block (host/fd_ed25519_hip_engine.c, dropin_run) and the
+     landed in that block (host/fd_ed25519_hip_dropin.c, dropin_wait) and the
      next call restages it; a kernel added after dsm16 that reads the block
      would break that silently. */
   if (threadIdx.x == 0u) p.out[p.base + j] = (int8_t)code;

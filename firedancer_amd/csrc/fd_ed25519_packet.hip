@@ -14,7 +14,7 @@
             that is not judged leaves a dummy slot (zero signature and key,
             empty message) whose verify code nothing reads.
      verify the engine's phases over the n slots
-            (host/fd_ed25519_hip_engine.c)
+            (host/fd_ed25519_hip_fronts.c)
      finish the stage's code, else ERR_SIGNATURE for a verify code other
             than success, else 0; the optional verify codes
 

@@ -4,7 +4,7 @@
    signs and each shred's inclusion proof -- the inverse of fd_shred_core.h's
    walk -- restated once and compiled three ways: into the device tree kernel
    (fd_ed25519_fec.hip, hipcc: the rules; the kernel hashes with its own
-   SHA-256), into the host library (host/fd_ed25519_hip_engine.c, gcc:
+   SHA-256), into the host library (host/fd_ed25519_hip_fronts.c, gcc:
    fd_ed25519_hip_fec_root) and into the hostile input test's stand-alone
    program (tests/fec_walk_main.c, gcc with sanitizers).  Adds to
    fd_shred_core.h and changes nothing of it; the includer may define

@@ -1,7 +1,7 @@
 /* fd_front_work.h -- the device workspace of the fronts before the verify
    phases (fd_ed25519_hip_precompile_dev, _shreds_dev, _packets_dev, _crds_dev), carved
    out of the caller's 16-byte-aligned buffer.  Plain C11, host only, nothing
-   but pointer arithmetic: the engine (host/fd_ed25519_hip_engine.c) takes
+   but pointer arithmetic: the engine (host/fd_ed25519_hip_fronts.c) takes
    its kernels' arrays from here, and tests/front_work_main.c (the CRDS
    front's: tests/crds_work_main.c, the FEC seal's: tests/fec_work_main.c) holds every layout to the public
    FD_ED25519_HIP_*_WORK_BYTES macro a caller sizes the buffer with.  A layout has no padding: the elements only get smaller, so

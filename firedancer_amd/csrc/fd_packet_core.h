@@ -2,7 +2,7 @@
    fd_repair_recv_serv_packet decide for a signed control packet of fixed or
    nearly fixed layout before they call fd_ed25519_verify, restated once and
    compiled three ways: into the device stage kernel (fd_ed25519_packet.hip,
-   hipcc), into the host library (host/fd_ed25519_hip_engine.c, gcc:
+   hipcc), into the host library (host/fd_ed25519_hip_fronts.c, gcc:
    fd_ed25519_hip_packet_plan) and into the hostile input test's stand-alone
    program (tests/packet_walk_main.c, gcc with sanitizers).  The includer
    may define FD_PACKET_FN (the function qualifiers) and the readers

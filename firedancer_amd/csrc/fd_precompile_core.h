@@ -1,6 +1,6 @@
 /* fd_precompile_core.h -- the offsets walk of the Ed25519 precompile
    (fd_precompile_ed25519_verify) restated once, compiled three ways: into
-   the host library (host/fd_ed25519_hip_engine.c, gcc), into the device
+   the host library (host/fd_ed25519_hip_fronts.c, gcc), into the device
    staging kernel (fd_ed25519_txn.hip, hipcc) and into the hostile
    input test's stand-alone program (tests/precompile_walk_main.c, gcc with
    sanitizers), so all three lay out exactly the same entries.  Include

@@ -2,7 +2,7 @@
    shred that opens a FEC set, up to the root its leader signed, restated
    once and compiled three ways: into the device stage kernel
    (fd_ed25519_shred.hip, hipcc: the rules; the kernel hashes with its own
-   SHA-256), into the host library (host/fd_ed25519_hip_engine.c, gcc:
+   SHA-256), into the host library (host/fd_ed25519_hip_fronts.c, gcc:
    fd_ed25519_hip_shred_root) and into the hostile input test's stand-alone
    program (tests/shred_walk_main.c, gcc with sanitizers).  The includer may
    define FD_SHRED_FN (the function qualifiers).

@@ -1,0 +1,635 @@
+/* fd_ed25519_hip_fronts.c -- the fronts before the verify phases
+   (include/fd_ed25519_hip.h Parts 2b-2f): stage kernel, verify_common,
+   finish kernel in a *_dev; pack, upload, *_dev, download, synchronise in a
+   *_host ("The shape of a front"); and the rules the stage
+   kernels run, on the host (*_count, *_plan, *_root).  Part of the engine:
+   the *_host wrappers stage in its pinned buffers
+   (fd_ed25519_hip_engine_fields.h). */
+
+#define _GNU_SOURCE
+#include "fd_ed25519_hip_engine_fields.h"
+#include "../../../include/fd_ed25519_hip_tile.h"   /* fd_ed25519_hip_txn_t, for the parse core */
+#include "../fd_txn_parse_core.h"
+#include "../fd_precompile_core.h"
+#include "../fd_shred_core.h"
+#include "../fd_packet_core.h"
+#include "../fd_crds_core.h"
+#include "../fd_fec_core.h"
+#include "../fd_front_work.h"
+
+#include <string.h>
+
+/* What an entry point does before any work.  Returns 1 to go on (the device
+   set, *st the call's stream), else the call's result: OK for an empty
+   batch, ERR_INVAL for a missing argument (args_ok: the caller's NULL and
+   range checks) or when one of the pointers or-ed into aligned16 (names, for
+   the message) is off a 16-byte boundary. */
+static int
+front_begin( fd_ed25519_hip_engine_t * e, unsigned long n, int args_ok, uintptr_t aligned16, char const * names,
+             void * stream, hipStream_t * st ) {
+  if( !e ) return FD_ED25519_HIP_ERR_INVAL;
+  if( !n ) return FD_ED25519_HIP_OK;
+  if( !args_ok ) return FD_ED25519_HIP_ERR_INVAL;
+  if( aligned16 & 15UL ) {
+    fd_ed25519_hip_private_set_errorf( "%s must be 16-byte aligned", names );
+    return FD_ED25519_HIP_ERR_INVAL;
+  }
+  *st = stream ? (hipStream_t)stream : e->stream;
+  HIPCHK( hipSetDevice( e->device ), "hipSetDevice" );
+  return 1;
+}
+
+/* the layout the kernels are about to write against the size the caller was told to allocate */
+static int
+front_work_fits( uint64_t end, uint64_t public_bytes, char const * what ) {
+  if( end<=public_bytes ) return FD_ED25519_HIP_OK;
+  fd_ed25519_hip_private_set_errorf( "%s workspace: %lu bytes laid out, %lu public", what, (unsigned long)end,
+                                     (unsigned long)public_bytes );
+  return FD_ED25519_HIP_ERR_INVAL;
+}
+
+/* device-only buffer grown on demand, like grow_pair */
+static int
+grow_dev( uint8_t ** d, uint64_t * cap, uint64_t need ) {
+  if( need<=*cap ) return FD_ED25519_HIP_OK;
+  uint64_t ncap = *cap ? *cap : 4096UL;
+  while( ncap<need ) ncap *= 2UL;
+  hipFree( *d ); *d = NULL; *cap = 0UL;
+  HIPCHK( hipMalloc( (void **)d, ncap ), "hipMalloc" );
+  *cap = ncap;
+  return FD_ED25519_HIP_OK;
+}
+
+/* a pass of a host wrapper: room for its item bytes (with 64 bytes behind the last) and its in and out blocks */
+static int
+front_room( fd_ed25519_hip_engine_t * e, uint64_t item_bytes, uint64_t in_bytes, uint64_t out_bytes ) {
+  int err;
+  if( (err = fd_ed25519_hip_private_stage_msgs( e, item_bytes )) ) return err;
+  if( (err = fd_ed25519_hip_private_grow_pair( (void **)&e->h_fr_in, (void **)&e->d_fr_in, &e->fr_in_cap, in_bytes, 1UL )) ) return err;
+  return fd_ed25519_hip_private_grow_pair( (void **)&e->h_fr_out, (void **)&e->d_fr_out, &e->fr_out_cap, out_bytes, 1UL );
+}
+
+/* ... the items [off[i], off[i]+sz[i]) back to back in the pinned item staging, their places and true sizes in
+   h_off and h_sz; an item of more than cap bytes travels as its first over bytes.  Returns the bytes packed */
+static uint64_t
+front_pack( fd_ed25519_hip_engine_t * e, uint64_t m, unsigned char const * items, unsigned long const * off,
+            unsigned int const * sz, uint64_t cap, uint64_t over, uint64_t * h_off, uint32_t * h_sz ) {
+  uint64_t pos = 0UL;
+  for( uint64_t i=0UL; i<m; i++ ) {
+    uint64_t cp = sz[i]<=cap ? sz[i] : over;
+    if( cp ) memcpy( e->h_msgs + pos, items + off[i], cp );
+    h_off[i] = pos;
+    h_sz [i] = sz[i];
+    pos += cp;
+  }
+  return pos;
+}
+
+/* ... the items and the in block to the device; the out block back, with the stream drained */
+static int
+front_upload( fd_ed25519_hip_engine_t * e, uint64_t item_bytes, uint64_t in_bytes, hipStream_t st ) {
+  HIPCHK( hipMemcpyAsync( e->d_msgs, e->h_msgs, item_bytes ? item_bytes : 1UL, hipMemcpyHostToDevice, st ), "H2D front items" );
+  HIPCHK( hipMemcpyAsync( e->d_fr_in, e->h_fr_in, in_bytes, hipMemcpyHostToDevice, st ), "H2D front in" );
+  return FD_ED25519_HIP_OK;
+}
+
+static int
+front_download( fd_ed25519_hip_engine_t * e, uint64_t out_bytes, hipStream_t st ) {
+  HIPCHK( hipMemcpyAsync( e->h_fr_out, e->d_fr_out, out_bytes, hipMemcpyDeviceToHost, st ), "D2H front out" );
+  HIPCHK( hipStreamSynchronize( st ), "front" );
+  return FD_ED25519_HIP_OK;
+}
+
+/* ---- Ed25519 precompile instructions (include/fd_ed25519_hip.h Part 2b) -- */
+
+_Static_assert( FD_ED25519_HIP_PRECOMPILE_ENT_MAX==FD_PRECOMPILE_CORE_ENT_MAX, "entry bound" );
+_Static_assert( FD_ED25519_HIP_PRECOMPILE_ERR_SIGNATURE==FD_PRECOMPILE_CORE_ERR_SIGNATURE &&
+                FD_ED25519_HIP_PRECOMPILE_ERR_DATA_OFFSET==FD_PRECOMPILE_CORE_ERR_DATA_OFFSET &&
+                FD_ED25519_HIP_PRECOMPILE_ERR_INSTR_DATA_SIZE==FD_PRECOMPILE_CORE_ERR_INSTR_DATA_SIZE,
+                "public and core precompile codes differ" );
+/* the plan's entries are the core's, copied as bytes */
+_Static_assert( sizeof(fd_ed25519_hip_precompile_ent_t)==sizeof(fd_precompile_core_ent_t) &&
+                offsetof(fd_ed25519_hip_precompile_ent_t,pre    )==offsetof(fd_precompile_core_ent_t,pre    ) &&
+                offsetof(fd_ed25519_hip_precompile_ent_t,sig_off)==offsetof(fd_precompile_core_ent_t,sig_off) &&
+                offsetof(fd_ed25519_hip_precompile_ent_t,pub_off)==offsetof(fd_precompile_core_ent_t,pub_off) &&
+                offsetof(fd_ed25519_hip_precompile_ent_t,msg_off)==offsetof(fd_precompile_core_ent_t,msg_off) &&
+                offsetof(fd_ed25519_hip_precompile_ent_t,msg_sz )==offsetof(fd_precompile_core_ent_t,msg_sz ),
+                "plan entry layout" );
+
+/* count and plan: the walk the stage kernel runs, on the host (no GPU) */
+unsigned
+fd_ed25519_hip_precompile_count( unsigned char const * payload, unsigned long payload_sz ) {
+  fd_precompile_core_sum_t sum;
+  int parsed;
+  fd_precompile_core_plan( payload, payload_sz, NULL, 0UL, &sum, &parsed );
+  return sum.ent_cnt;
+}
+
+int
+fd_ed25519_hip_precompile_plan( unsigned char const * payload, unsigned long payload_sz,
+                                fd_ed25519_hip_precompile_ent_t * ents, unsigned long cap,
+                                signed char * parse_or_header_code, unsigned char * instr ) {
+  fd_precompile_core_sum_t sum;
+  int parsed;
+  int n = fd_precompile_core_plan( payload, payload_sz, (fd_precompile_core_ent_t *)ents, ents ? cap : 0UL, &sum, &parsed );
+  if( parse_or_header_code )
+    *parse_or_header_code = (signed char)( !parsed ? FD_ED25519_HIP_PRECOMPILE_PARSE_FAILED
+                                         : sum.hdr_instr!=0xFF ? FD_ED25519_HIP_PRECOMPILE_ERR_INSTR_DATA_SIZE : 0 );
+  if( instr ) *instr = sum.hdr_instr;
+  return n;
+}
+
+int
+fd_ed25519_hip_precompile_dev( fd_ed25519_hip_engine_t * e, unsigned long ntxn, unsigned char const * payloads,
+                               unsigned long const * pay_off, unsigned int const * pay_sz,
+                               unsigned int const * ent_first, unsigned long n_ent, void * work,
+                               signed char * txn_out, unsigned char * instr_out, signed char * ent_out,
+                               void * stream ) {
+  hipStream_t st;
+  int err = front_begin( e, ntxn, payloads && pay_off && pay_sz && ent_first && work && txn_out && instr_out &&
+                                  n_ent<=ntxn*FD_ED25519_HIP_PRECOMPILE_ENT_MAX,
+                         (uintptr_t)work, "precompile work", stream, &st );
+  if( err<=0 ) return err;
+  front_work_t w;
+  err = front_work_fits( front_work_precompile( work, ntxn, n_ent, &w ), FD_ED25519_HIP_PRECOMPILE_WORK_BYTES( ntxn, n_ent ),
+                         "precompile" );
+  if( err ) return err;
+  fd_ed25519_precompile_stage_params_t sp = { 0 };
+  sp.payloads = payloads; sp.pay_off = (uint64_t const *)pay_off; sp.pay_sz = pay_sz; sp.ent_first = ent_first;
+  sp.ntxn = ntxn; sp.n_ent = n_ent;
+  sp.sigs = w.sigs; sp.pubs = w.pubs; sp.msg_off = w.msg_off; sp.msg_sz = w.msg_sz; sp.pre = w.pre;
+  sp.ent_instr = w.ent_instr; sp.status = w.status; sp.hdr_instr = w.hdr_instr; sp.hdr_pos = w.hdr_pos;
+  HIPCHK( (hipError_t)fd_ed25519_hip_launch_precompile_stage( &sp, st ), "precompile_stage launch" );
+  if( n_ent ) {
+    err = fd_ed25519_hip_private_verify_common( e, n_ent, payloads, (unsigned long const *)w.msg_off, w.msg_sz, NULL, w.sigs, w.pubs,
+                         (signed char *)w.codes, st );
+    if( err ) return err;
+  }
+  fd_ed25519_precompile_finish_params_t fp = { 0 };
+  fp.codes = w.codes; fp.pre = w.pre; fp.ent_instr = w.ent_instr; fp.status = w.status;
+  fp.hdr_instr = w.hdr_instr; fp.hdr_pos = w.hdr_pos; fp.ent_first = ent_first; fp.ntxn = ntxn; fp.n_ent = n_ent;
+  fp.txn_out = (int8_t *)txn_out; fp.instr_out = instr_out; fp.ent_out = (int8_t *)ent_out;
+  HIPCHK( (hipError_t)fd_ed25519_hip_launch_precompile_finish( &fp, st ), "precompile_finish launch" );
+  return FD_ED25519_HIP_OK;
+}
+
+/* one pass over ntxn: the entries are counted from the packed copies, the ones the device will read */
+int
+fd_ed25519_hip_precompile_host( fd_ed25519_hip_engine_t * e, unsigned long ntxn, unsigned char const * payloads,
+                                unsigned long const * pay_off, unsigned int const * pay_sz, signed char * txn_out,
+                                unsigned char * instr_out ) {
+  hipStream_t st;
+  int err = front_begin( e, ntxn, payloads && pay_off && pay_sz && txn_out && instr_out, 0UL, NULL, NULL, &st );
+  if( err<=0 ) return err;
+  uint64_t bytes = 0UL;
+  for( uint64_t t=0UL; t<ntxn; t++ ) bytes += pay_sz[t];
+  /* in: pay_off u64 [ntxn], ent_first u32 [ntxn+1], pay_sz u32 [ntxn]; out: txn_out, instr_out [ntxn] */
+  uint64_t in_bytes = 16UL*ntxn + 4UL, first_at = 8UL*ntxn, sz_at = 12UL*ntxn + 4UL;
+  if( (err = front_room( e, bytes, in_bytes, 2UL*ntxn )) ) return err;
+  uint64_t * h_off   = (uint64_t *)e->h_fr_in;
+  uint32_t * h_first = (uint32_t *)( e->h_fr_in + first_at );
+  front_pack( e, ntxn, payloads, pay_off, pay_sz, UINT64_MAX, 0UL, h_off, (uint32_t *)( e->h_fr_in + sz_at ) );
+  uint64_t n_ent = 0UL;
+  for( uint64_t t=0UL; t<ntxn; t++ ) {
+    h_first[t] = (uint32_t)n_ent;
+    n_ent += fd_ed25519_hip_precompile_count( e->h_msgs + h_off[t], pay_sz[t] );
+  }
+  h_first[ntxn] = (uint32_t)n_ent;
+  if( (err = grow_dev( &e->d_fr_work, &e->fr_work_cap, FD_ED25519_HIP_PRECOMPILE_WORK_BYTES( ntxn, n_ent ) )) ) return err;
+  if( (err = front_upload( e, bytes, in_bytes, st )) ) return err;
+  if( (err = fd_ed25519_hip_precompile_dev( e, ntxn, e->d_msgs, (unsigned long const *)e->d_fr_in,
+                                            (unsigned int const *)( e->d_fr_in + sz_at ),
+                                            (unsigned int const *)( e->d_fr_in + first_at ), n_ent, e->d_fr_work,
+                                            (signed char *)e->d_fr_out, e->d_fr_out + ntxn, NULL, st )) ) return err;
+  if( (err = front_download( e, 2UL*ntxn, st )) ) return err;
+  memcpy( txn_out,   e->h_fr_out,        ntxn );
+  memcpy( instr_out, e->h_fr_out + ntxn, ntxn );
+  return FD_ED25519_HIP_OK;
+}
+
+/* ---- leader signatures of Merkle shreds (include/fd_ed25519_hip.h Part 2c) -- */
+
+_Static_assert( FD_ED25519_HIP_SHRED_OK==FD_SHRED_CORE_OK && FD_ED25519_HIP_SHRED_ERR_PARSE==FD_SHRED_CORE_ERR_PARSE &&
+                FD_ED25519_HIP_SHRED_UNSUPPORTED==FD_SHRED_CORE_UNSUPPORTED &&
+                FD_ED25519_HIP_SHRED_ERR_HEADER==FD_SHRED_CORE_ERR_HEADER &&
+                FD_ED25519_HIP_SHRED_ERR_SIGNATURE==FD_SHRED_CORE_ERR_SIGNATURE,
+                "public and core shred codes differ" );
+
+/* the rules and the hashes the stage kernel runs, on the host (no GPU) */
+int
+fd_ed25519_hip_shred_root( unsigned char const * shred, unsigned long sz, unsigned char * root ) {
+  return fd_shred_core_root( shred, sz, root );
+}
+
+int
+fd_ed25519_hip_shreds_dev( fd_ed25519_hip_engine_t * e, unsigned long n, unsigned char const * shreds,
+                           unsigned long const * shred_off, unsigned int const * shred_sz,
+                           unsigned char const * leaders, void * work, signed char * out, unsigned char * roots,
+                           signed char * sig_out, void * stream ) {
+  hipStream_t st;
+  int err = front_begin( e, n, shreds && shred_off && shred_sz && leaders && work && out,
+                         (uintptr_t)work | (uintptr_t)leaders | (uintptr_t)roots | (uintptr_t)shreds,
+                         "shreds/leaders/work/roots", stream, &st );
+  if( err<=0 ) return err;
+  front_work_t w;
+  if( (err = front_work_fits( front_work_shred( work, n, &w ), FD_ED25519_HIP_SHRED_WORK_BYTES( n ), "shred" )) ) return err;
+  fd_ed25519_shred_stage_params_t sp = { 0 };
+  sp.shreds = shreds; sp.shred_off = (uint64_t const *)shred_off; sp.shred_sz = shred_sz; sp.n = n;
+  sp.sigs = w.sigs; sp.roots = w.pubs /* the keys are the leaders */; sp.msg_off = w.msg_off; sp.msg_sz = w.msg_sz; sp.pre = w.pre;
+  HIPCHK( (hipError_t)fd_ed25519_hip_launch_shred_stage( &sp, st ), "shred_stage launch" );
+  err = fd_ed25519_hip_private_verify_common( e, n, w.pubs, (unsigned long const *)w.msg_off, w.msg_sz, NULL, w.sigs, leaders,
+                       (signed char *)w.codes, st );
+  if( err ) return err;
+  fd_ed25519_shred_finish_params_t fp = { 0 };
+  fp.codes = w.codes; fp.pre = w.pre; fp.roots = w.pubs; fp.n = n;
+  fp.out = (int8_t *)out; fp.roots_out = roots; fp.sig_out = (int8_t *)sig_out;
+  HIPCHK( (hipError_t)fd_ed25519_hip_launch_shred_finish( &fp, st ), "shred_finish launch" );
+  return FD_ED25519_HIP_OK;
+}
+
+/* ---- signed gossip and repair control packets (include/fd_ed25519_hip.h Part 2d) -- */
+
+_Static_assert( FD_ED25519_HIP_PACKET_OK==FD_PACKET_CORE_OK && FD_ED25519_HIP_PACKET_ERR_PARSE==FD_PACKET_CORE_ERR_PARSE &&
+                FD_ED25519_HIP_PACKET_UNSUPPORTED==FD_PACKET_CORE_UNSUPPORTED &&
+                FD_ED25519_HIP_PACKET_ERR_SIGNATURE==FD_PACKET_CORE_ERR_SIGNATURE &&
+                FD_ED25519_HIP_PACKET_NOT_FOR_SELF==FD_PACKET_CORE_NOT_FOR_SELF &&
+                FD_ED25519_HIP_PROTO_GOSSIP==FD_PACKET_CORE_PROTO_GOSSIP &&
+                FD_ED25519_HIP_PROTO_REPAIR_SERV==FD_PACKET_CORE_PROTO_REPAIR_SERV &&
+                FD_ED25519_HIP_PACKET_MAX==FD_PACKET_CORE_MAX &&
+                sizeof(fd_ed25519_hip_packet_plan_t)==sizeof(fd_packet_core_plan_t),
+                "public and core packet constants differ" );
+
+static int
+packet_proto_ok( int proto ) {
+  return ( proto==FD_ED25519_HIP_PROTO_GOSSIP ) | ( proto==FD_ED25519_HIP_PROTO_REPAIR_SERV );
+}
+
+/* the rules the stage kernel runs, on the host (no GPU) */
+int
+fd_ed25519_hip_packet_plan( int proto, unsigned char const * pkt, unsigned long sz, unsigned char const self_key[ 32 ],
+                            fd_ed25519_hip_packet_plan_t * plan ) {
+  if( !packet_proto_ok( proto ) || !self_key || !plan ) return FD_ED25519_HIP_ERR_INVAL;
+  fd_packet_core_plan_t c;
+  int code = fd_packet_core_plan( proto, pkt, sz, self_key, &c );
+  memcpy( plan, &c, sizeof(c) );
+  return code;
+}
+
+int
+fd_ed25519_hip_packets_dev( fd_ed25519_hip_engine_t * e, int proto, unsigned long n, unsigned char const * pkts,
+                            unsigned long const * pkt_off, unsigned int const * pkt_sz, unsigned long pkt_bytes,
+                            unsigned char const self_key[ 32 ], void * work, signed char * out, signed char * sig_out,
+                            void * stream ) {
+  if( !packet_proto_ok( proto ) || !self_key ) return FD_ED25519_HIP_ERR_INVAL;   /* of an empty batch too */
+  hipStream_t st;
+  int err = front_begin( e, n, pkts && pkt_off && pkt_sz && work && out, (uintptr_t)work | (uintptr_t)pkts, "pkts/work",
+                         stream, &st );
+  if( err<=0 ) return err;
+  front_work_t w;
+  err = front_work_fits( front_work_packet( work, n, pkt_bytes, &w ), FD_ED25519_HIP_PACKET_WORK_BYTES( n, pkt_bytes ),
+                         "packet" );
+  if( err ) return err;
+  fd_ed25519_packet_stage_params_t sp = { 0 };
+  sp.pkts = pkts; sp.pkt_off = (uint64_t const *)pkt_off; sp.pkt_sz = pkt_sz; sp.n = n; sp.pkt_bytes = pkt_bytes;
+  memcpy( sp.self_key, self_key, 32UL );
+  sp.proto = proto;
+  sp.sigs = w.sigs; sp.pubs = w.pubs; sp.msgs = w.msgs; sp.msg_off = w.msg_off; sp.msg_sz = w.msg_sz; sp.pre = w.pre;
+  HIPCHK( (hipError_t)fd_ed25519_hip_launch_packet_stage( &sp, st ), "packet_stage launch" );
+  err = fd_ed25519_hip_private_verify_common( e, n, w.msgs, (unsigned long const *)w.msg_off, w.msg_sz, NULL, w.sigs, w.pubs,
+                       (signed char *)w.codes, st );
+  if( err ) return err;
+  fd_ed25519_packet_finish_params_t fp = { 0 };
+  fp.codes = w.codes; fp.pre = w.pre; fp.n = n; fp.out = (int8_t *)out; fp.sig_out = (int8_t *)sig_out;
+  HIPCHK( (hipError_t)fd_ed25519_hip_launch_packet_finish( &fp, st ), "packet_finish launch" );
+  return FD_ED25519_HIP_OK;
+}
+
+/* ---- shreds_host and packets_host ---------------------------------------- */
+
+/* items per pass: bounds the pinned staging (20 MiB of item bytes) whatever n is */
+#define FRONT_HOST_CHUNK 16384UL
+
+/* The round trip of shreds (leaders given) and of packets (leaders NULL),
+   pass by pass.  A shred pass has the leaders, 32 bytes each, in front of
+   its in block (off u64 [m], sz u32 [m]) and the roots, 32 bytes each, in
+   front of its out block (codes [m]).  No shred rule reads a byte at or past
+   FD_SHRED_MAX_SZ, so a longer shred travels as its head and its true size;
+   no packet rule reads a packet of more than FD_ED25519_HIP_PACKET_MAX bytes
+   at all: it travels as its true size alone, and leaves the packed range. */
+static int
+front_items_host( fd_ed25519_hip_engine_t * e, hipStream_t st, unsigned long n, unsigned char const * items,
+                  unsigned long const * off, unsigned int const * sz, unsigned char const * leaders, int proto,
+                  unsigned char const * self_key, signed char * out, unsigned char * roots ) {
+  uint64_t cap  = leaders ? FD_SHRED_CORE_MAX_SZ : FD_PACKET_CORE_MAX, over = leaders ? cap : 0UL;
+  uint64_t lead = leaders ? 32UL : 0UL;
+  int err;
+  for( uint64_t base=0UL; base<n; base+=FRONT_HOST_CHUNK ) {
+    uint64_t m = n-base<FRONT_HOST_CHUNK ? n-base : FRONT_HOST_CHUNK;
+    uint64_t off_at = lead*m, sz_at = off_at + 8UL*m, in_bytes = sz_at + 4UL*m, out_bytes = lead*m + m;
+    if( (err = front_room( e, m*cap, in_bytes, out_bytes )) ) return err;
+    if( leaders ) memcpy( e->h_fr_in, leaders + 32UL*base, 32UL*m );
+    uint64_t pos = front_pack( e, m, items, off+base, sz+base, cap, over, (uint64_t *)( e->h_fr_in + off_at ),
+                               (uint32_t *)( e->h_fr_in + sz_at ) );
+    uint64_t work = leaders ? FD_ED25519_HIP_SHRED_WORK_BYTES( m ) : FD_ED25519_HIP_PACKET_WORK_BYTES( m, pos );
+    if( (err = grow_dev( &e->d_fr_work, &e->fr_work_cap, work )) ) return err;
+    if( (err = front_upload( e, pos, in_bytes, st )) ) return err;
+    unsigned long const * d_off   = (unsigned long const *)( e->d_fr_in + off_at );
+    unsigned int const *  d_sz    = (unsigned int const *)( e->d_fr_in + sz_at );
+    signed char *         d_codes = (signed char *)( e->d_fr_out + lead*m );
+    err = leaders ? fd_ed25519_hip_shreds_dev( e, m, e->d_msgs, d_off, d_sz, e->d_fr_in, e->d_fr_work, d_codes,
+                                               roots ? e->d_fr_out : NULL, NULL, st )
+                  : fd_ed25519_hip_packets_dev( e, proto, m, e->d_msgs, d_off, d_sz, pos, self_key, e->d_fr_work, d_codes,
+                                                NULL, st );
+    if( err ) return err;
+    if( (err = front_download( e, out_bytes, st )) ) return err;
+    memcpy( out + base, e->h_fr_out + lead*m, m );
+    if( roots ) memcpy( roots + 32UL*base, e->h_fr_out, 32UL*m );
+  }
+  return FD_ED25519_HIP_OK;
+}
+
+int
+fd_ed25519_hip_shreds_host( fd_ed25519_hip_engine_t * e, unsigned long n, unsigned char const * shreds,
+                            unsigned long const * shred_off, unsigned int const * shred_sz,
+                            unsigned char const * leaders, signed char * out, unsigned char * roots ) {
+  hipStream_t st;
+  int err = front_begin( e, n, shreds && shred_off && shred_sz && leaders && out, 0UL, NULL, NULL, &st );
+  if( err<=0 ) return err;
+  return front_items_host( e, st, n, shreds, shred_off, shred_sz, leaders, 0, NULL, out, roots );
+}
+
+int
+fd_ed25519_hip_packets_host( fd_ed25519_hip_engine_t * e, int proto, unsigned long n, unsigned char const * pkts,
+                             unsigned long const * pkt_off, unsigned int const * pkt_sz,
+                             unsigned char const self_key[ 32 ], signed char * out ) {
+  if( !packet_proto_ok( proto ) || !self_key ) return FD_ED25519_HIP_ERR_INVAL;
+  hipStream_t st;
+  int err = front_begin( e, n, pkts && pkt_off && pkt_sz && out, 0UL, NULL, NULL, &st );
+  if( err<=0 ) return err;
+  return front_items_host( e, st, n, pkts, pkt_off, pkt_sz, NULL, proto, self_key, out, NULL );
+}
+
+/* ---- CRDS values of gossip pull responses and push messages (include/fd_ed25519_hip.h Part 2e) -- */
+
+_Static_assert( FD_ED25519_HIP_CRDS_OK==FD_CRDS_CORE_OK && FD_ED25519_HIP_CRDS_ERR_PARSE==FD_CRDS_CORE_ERR_PARSE &&
+                FD_ED25519_HIP_CRDS_UNSUPPORTED==FD_CRDS_CORE_UNSUPPORTED &&
+                FD_ED25519_HIP_CRDS_ERR_SIGNATURE==FD_CRDS_CORE_ERR_SIGNATURE &&
+                FD_ED25519_HIP_CRDS_OWN==FD_CRDS_CORE_OWN && FD_ED25519_HIP_CRDS_VAL_MAX==FD_CRDS_CORE_VAL_MAX &&
+                FD_ED25519_HIP_PACKET_MAX==FD_CRDS_CORE_MAX &&
+                FD_CRDS_CORE_HDR_SZ + FD_CRDS_CORE_VAL_MAX*FD_CRDS_CORE_VAL_MIN<=FD_CRDS_CORE_MAX &&
+                FD_CRDS_CORE_HDR_SZ + ( FD_CRDS_CORE_VAL_MAX+1UL )*FD_CRDS_CORE_VAL_MIN>FD_CRDS_CORE_MAX,
+                "public and core CRDS constants differ" );
+/* the plan's values are the core's, copied as bytes */
+_Static_assert( sizeof(fd_ed25519_hip_crds_val_t)==sizeof(fd_crds_core_val_t) &&
+                offsetof(fd_ed25519_hip_crds_val_t,disc   )==offsetof(fd_crds_core_val_t,disc   ) &&
+                offsetof(fd_ed25519_hip_crds_val_t,sig_off)==offsetof(fd_crds_core_val_t,sig_off) &&
+                offsetof(fd_ed25519_hip_crds_val_t,key_off)==offsetof(fd_crds_core_val_t,key_off) &&
+                offsetof(fd_ed25519_hip_crds_val_t,msg_off)==offsetof(fd_crds_core_val_t,msg_off) &&
+                offsetof(fd_ed25519_hip_crds_val_t,msg_sz )==offsetof(fd_crds_core_val_t,msg_sz ) &&
+                offsetof(fd_ed25519_hip_crds_val_t,pre    )==offsetof(fd_crds_core_val_t,pre    ),
+                "plan value layout" );
+
+/* count and plan: the walk the stage kernel runs, on the host (no GPU) */
+unsigned
+fd_ed25519_hip_crds_count( unsigned char const * pkt, unsigned long sz ) {
+  fd_crds_core_idx_t idx;
+  fd_crds_core_walk( pkt, sz, &idx );
+  return idx.cnt;
+}
+
+int
+fd_ed25519_hip_crds_plan( unsigned char const * pkt, unsigned long sz, unsigned char const self_key[ 32 ],
+                          fd_ed25519_hip_crds_val_t * vals, unsigned long cap, signed char * pkt_code ) {
+  if( !self_key ) return FD_ED25519_HIP_ERR_INVAL;
+  fd_crds_core_idx_t idx;
+  int code = fd_crds_core_walk( pkt, sz, &idx );
+  if( pkt_code ) *pkt_code = (signed char)code;
+  unsigned k = 0U;
+  for( ; vals && k<idx.cnt && k<cap; k++ ) {
+    fd_crds_core_val_t v = { 0 };
+    fd_crds_core_value( pkt, sz, &idx, k, self_key, &v );
+    memcpy( vals + k, &v, sizeof(v) );
+  }
+  return (int)k;
+}
+
+int
+fd_ed25519_hip_crds_dev( fd_ed25519_hip_engine_t * e, unsigned long n, unsigned char const * pkts,
+                         unsigned long const * pkt_off, unsigned int const * pkt_sz, unsigned long pkt_bytes,
+                         unsigned char const self_key[ 32 ], unsigned int const * val_first, unsigned long n_val,
+                         void * work, signed char * pkt_out, signed char * val_out, signed char * sig_out,
+                         unsigned char * hash_out, void * stream ) {
+  if( !self_key ) return FD_ED25519_HIP_ERR_INVAL;   /* of an empty batch too */
+  hipStream_t st;
+  int err = front_begin( e, n, pkts && pkt_off && pkt_sz && val_first && work && pkt_out && ( val_out || !n_val ) &&
+                               n_val<=n*FD_ED25519_HIP_CRDS_VAL_MAX && !( (uintptr_t)pkts & 3UL ) && !( (uintptr_t)hash_out & 3UL ),
+                         (uintptr_t)work, "crds work", stream, &st );
+  if( err<=0 ) return err;
+  front_work_t w;
+  err = front_work_fits( front_work_crds( work, n, n_val, &w ), FD_ED25519_HIP_CRDS_WORK_BYTES( n, n_val ), "crds" );
+  if( err ) return err;
+  fd_ed25519_crds_stage_params_t sp = { 0 };
+  sp.pkts = pkts; sp.pkt_off = (uint64_t const *)pkt_off; sp.pkt_sz = pkt_sz; sp.val_first = val_first;
+  sp.n = n; sp.n_val = n_val; sp.pkt_bytes = pkt_bytes;
+  memcpy( sp.self_key, self_key, 32UL );
+  sp.sigs = w.sigs; sp.pubs = w.pubs; sp.msg_off = w.msg_off; sp.msg_sz = w.msg_sz; sp.val_sz = w.val_sz; sp.pre = w.pre;
+  sp.status = w.status;
+  /* The stage fills the slots val_first reserves.  A val_first that is no prefix sum (it runs backwards, leaves n_val or
+     skips slots) leaves slots no lane fills, and the verify phases read every slot's message offset: empty messages at
+     offset 0 and BAD_RESERVATION for all, ahead of the stage (msg_off, msg_sz, val_sz and codes are adjacent). */
+  if( n_val ) {
+    HIPCHK( hipMemsetAsync( w.msg_off, 0, 17UL*n_val, st ), "crds slots memset" );
+    HIPCHK( hipMemsetAsync( w.pre, FD_ED25519_HIP_CRDS_BAD_RESERVATION & 0xFF, n_val, st ), "crds slots memset" );
+  }
+  HIPCHK( (hipError_t)fd_ed25519_hip_launch_crds_stage( &sp, st ), "crds_stage launch" );
+  if( n_val ) {
+    err = fd_ed25519_hip_private_verify_common( e, n_val, pkts, (unsigned long const *)w.msg_off, w.msg_sz, NULL, w.sigs, w.pubs,
+                         (signed char *)w.codes, st );
+    if( err ) return err;
+  }
+  fd_ed25519_crds_finish_params_t fp = { 0 };
+  fp.codes = w.codes; fp.pre = w.pre; fp.status = w.status; fp.n = n; fp.n_val = n_val;
+  fp.pkt_out = (int8_t *)pkt_out; fp.val_out = (int8_t *)val_out; fp.sig_out = (int8_t *)sig_out;
+  HIPCHK( (hipError_t)fd_ed25519_hip_launch_crds_finish( &fp, st ), "crds_finish launch" );
+  if( hash_out ) {
+    fd_ed25519_crds_hash_params_t hp = { 0 };
+    hp.pkts = pkts; hp.msg_off = w.msg_off; hp.val_sz = w.val_sz; hp.n_val = n_val; hp.hash_out = hash_out;
+    HIPCHK( (hipError_t)fd_ed25519_hip_launch_crds_hash( &hp, st ), "crds_hash launch" );
+  }
+  return FD_ED25519_HIP_OK;
+}
+
+/* pass by pass, as front_items_host; a pass counts the values from the packed copies, the ones the device will read.
+   in: off u64 [m], val_first u32 [m+1], sz u32 [m]; out: hashes [nv][32], value codes [nv], packet codes [m] */
+int
+fd_ed25519_hip_crds_host( fd_ed25519_hip_engine_t * e, unsigned long n, unsigned char const * pkts,
+                          unsigned long const * pkt_off, unsigned int const * pkt_sz, unsigned char const self_key[ 32 ],
+                          unsigned int * val_first_out, signed char * pkt_out, signed char * val_out,
+                          unsigned char * hash_out ) {
+  if( !self_key ) return FD_ED25519_HIP_ERR_INVAL;
+  if( e && val_first_out ) val_first_out[ 0 ] = 0U;
+  hipStream_t st;
+  int err = front_begin( e, n, pkts && pkt_off && pkt_sz && val_first_out && pkt_out && val_out, 0UL, NULL, NULL, &st );
+  if( err<=0 ) return err;
+  uint64_t total = 0UL;
+  for( uint64_t base=0UL; base<n; base+=FRONT_HOST_CHUNK ) {
+    uint64_t m = n-base<FRONT_HOST_CHUNK ? n-base : FRONT_HOST_CHUNK;
+    uint64_t first_at = 8UL*m, sz_at = 12UL*m + 4UL, in_bytes = 16UL*m + 4UL;
+    uint64_t out_max = 33UL*m*FD_ED25519_HIP_CRDS_VAL_MAX + m;
+    if( (err = front_room( e, m*FD_CRDS_CORE_MAX, in_bytes, out_max )) ) return err;
+    uint64_t * h_off   = (uint64_t *)e->h_fr_in;
+    uint32_t * h_first = (uint32_t *)( e->h_fr_in + first_at );
+    uint32_t * h_sz    = (uint32_t *)( e->h_fr_in + sz_at );
+    uint64_t pos = front_pack( e, m, pkts, pkt_off+base, pkt_sz+base, FD_CRDS_CORE_MAX, 0UL, h_off, h_sz );
+    uint64_t nv = 0UL;
+    for( uint64_t i=0UL; i<m; i++ ) {
+      h_first[i] = (uint32_t)nv;
+      val_first_out[ base+i ] = (unsigned int)( total + nv );
+      /* a packet of more than PACKET_MAX bytes travels as its size alone: the walk rejects the size unread */
+      nv += fd_ed25519_hip_crds_count( e->h_msgs + h_off[i], h_sz[i] );
+    }
+    h_first[m] = (uint32_t)nv;
+    val_first_out[ base+m ] = (unsigned int)( total + nv );
+    uint64_t hash_bytes = hash_out ? 32UL*nv : 0UL, out_bytes = hash_bytes + nv + m;
+    if( (err = grow_dev( &e->d_fr_work, &e->fr_work_cap, FD_ED25519_HIP_CRDS_WORK_BYTES( m, nv ) )) ) return err;
+    if( (err = front_upload( e, pos, in_bytes, st )) ) return err;
+    err = fd_ed25519_hip_crds_dev( e, m, e->d_msgs, (unsigned long const *)e->d_fr_in,
+                                   (unsigned int const *)( e->d_fr_in + sz_at ), pos, self_key,
+                                   (unsigned int const *)( e->d_fr_in + first_at ), nv, e->d_fr_work,
+                                   (signed char *)( e->d_fr_out + hash_bytes + nv ), (signed char *)( e->d_fr_out + hash_bytes ),
+                                   NULL, hash_out ? e->d_fr_out : NULL, st );
+    if( err ) return err;
+    if( (err = front_download( e, out_bytes, st )) ) return err;
+    if( hash_out ) memcpy( hash_out + 32UL*total, e->h_fr_out, hash_bytes );
+    memcpy( val_out + total, e->h_fr_out + hash_bytes, nv );
+    memcpy( pkt_out + base, e->h_fr_out + hash_bytes + nv, m );
+    total += nv;
+  }
+  return FD_ED25519_HIP_OK;
+}
+
+/* ---- sealing a leader's FEC sets (include/fd_ed25519_hip.h Part 2f) ------ */
+
+_Static_assert( FD_ED25519_HIP_FEC_OK==FD_FEC_CORE_OK && FD_ED25519_HIP_FEC_ERR_PARSE==FD_FEC_CORE_ERR_PARSE &&
+                FD_ED25519_HIP_FEC_UNSUPPORTED==FD_FEC_CORE_UNSUPPORTED && FD_ED25519_HIP_FEC_ERR_SET==FD_FEC_CORE_ERR_SET &&
+                FD_ED25519_HIP_FEC_ERR_SET==FD_ED25519_HIP_SHRED_ERR_HEADER &&
+                FD_ED25519_HIP_FEC_SET_MAX==FD_FEC_CORE_CNT_MAX,
+                "public and core FEC constants differ" );
+
+/* the rules and the tree the tree kernel runs, on the host (no GPU) */
+int
+fd_ed25519_hip_fec_root( unsigned char const * shreds, unsigned long const * shred_off, unsigned int const * shred_sz,
+                         unsigned long cnt, unsigned char * root, unsigned char * proofs ) {
+  if( !root ) return FD_ED25519_HIP_ERR_INVAL;
+  return fd_fec_core_root( shreds, shred_off, shred_sz, cnt, root, proofs );
+}
+
+int
+fd_ed25519_hip_fec_seal_dev( fd_ed25519_hip_engine_t * e, unsigned long n, unsigned char * shreds,
+                             unsigned long const * shred_off, unsigned int const * shred_sz, unsigned long n_set,
+                             unsigned int const * set_first, unsigned char const * privs, void * work,
+                             signed char * set_out, unsigned char * roots, unsigned char * sigs, void * stream ) {
+  hipStream_t st;
+  /* the batch is its sets: none is a no-op whatever n is; a signature copy needs the keys */
+  int err = front_begin( e, n_set, set_first && work && set_out && ( !n || ( shreds && shred_off && shred_sz ) ) &&
+                                   n<=UINT32_MAX && n_set<=INT32_MAX && ( privs || !sigs ),
+                         (uintptr_t)work | (uintptr_t)privs | (uintptr_t)roots | (uintptr_t)sigs | (uintptr_t)shreds,
+                         "shreds/privs/work/roots/sigs", stream, &st );
+  if( err<=0 ) return err;
+  front_work_t w;
+  if( (err = front_work_fits( front_work_fec( work, n, n_set, &w ), FD_ED25519_HIP_FEC_WORK_BYTES( n, n_set ), "fec" )) ) return err;
+  /* no set has sealed a shred yet; the scatter reads every shred's entry */
+  if( n ) HIPCHK( hipMemsetAsync( w.set_of, 0xFF, 4UL*n, st ), "fec set_of memset" );
+  fd_ed25519_fec_tree_params_t tp = { 0 };
+  tp.shreds = shreds; tp.shred_off = (uint64_t const *)shred_off; tp.shred_sz = shred_sz; tp.n = n;
+  tp.set_first = set_first; tp.n_set = n_set;
+  tp.roots = w.roots; tp.msg_off = w.msg_off; tp.msg_sz = w.msg_sz; tp.set_of = w.set_of;
+  tp.set_out = (int8_t *)set_out; tp.roots_out = roots;
+  HIPCHK( (hipError_t)fd_ed25519_hip_launch_fec_tree( &tp, st ), "fec_tree launch" );
+  if( !privs ) return FD_ED25519_HIP_OK;   /* the keyguard split: the caller signs the roots elsewhere */
+  fd_ed25519_sign_params_t gp = { 0 };
+  gp.msgs = w.roots; gp.msg_off = w.msg_off; gp.msg_sz = w.msg_sz; gp.privs = privs;
+  gp.sigs = w.sigs; gp.pubs = w.pubs; gp.n = n_set; gp.btab = e->d_btab;
+  HIPCHK( (hipError_t)fd_ed25519_hip_launch_sign( &gp, st ), "fec sign launch" );
+  fd_ed25519_fec_scatter_params_t cp = { 0 };
+  cp.shreds = shreds; cp.shred_off = (uint64_t const *)shred_off; cp.n = n; cp.n_set = n_set;
+  cp.set_of = w.set_of; cp.sigs = w.sigs; cp.set_out = (int8_t const *)set_out; cp.sigs_out = sigs;
+  HIPCHK( (hipError_t)fd_ed25519_hip_launch_fec_scatter( &cp, st ), "fec_scatter launch" );
+  return FD_ED25519_HIP_OK;
+}
+
+/* Pass by pass, whole sets at a time: up to FRONT_HOST_CHUNK shreds and as
+   many sets.  A set whose range runs backwards, leaves [0, n) or holds more
+   than FEC_SET_MAX shreds travels as an empty set, which is the same code.
+   No rule reads and no kernel writes a byte at or past FD_SHRED_MAX_SZ, so a
+   longer shred travels as its head and its true size.
+   in: privs [ms][32], off u64 [m], set_first u32 [ms+1], sz u32 [m];
+   out: roots [ms][32], sigs [ms][64], codes [ms].  Of a sealed set's shreds
+   the signature (with privs) and the proof are copied back, nothing else. */
+int
+fd_ed25519_hip_fec_seal_host( fd_ed25519_hip_engine_t * e, unsigned long n, unsigned char * shreds,
+                              unsigned long const * shred_off, unsigned int const * shred_sz, unsigned long n_set,
+                              unsigned int const * set_first, unsigned char const * privs, signed char * set_out,
+                              unsigned char * roots, unsigned char * sigs ) {
+  hipStream_t st;
+  int err = front_begin( e, n_set, set_first && set_out && ( !n || ( shreds && shred_off && shred_sz ) ) && n<=UINT32_MAX &&
+                                   ( privs || !sigs ), 0UL, NULL, NULL, &st );
+  if( err<=0 ) return err;
+  for( uint64_t k0=0UL; k0<n_set; ) {
+    uint64_t k1 = k0, m = 0UL;
+    for( ; k1<n_set && k1-k0<FRONT_HOST_CHUNK; k1++ ) {
+      uint64_t first = set_first[k1], last = set_first[k1+1UL];
+      uint64_t cnt = ( first<=last && last<=n && last-first<=FD_FEC_CORE_CNT_MAX ) ? last-first : 0UL;
+      if( m+cnt>FRONT_HOST_CHUNK ) break;
+      m += cnt;
+    }
+    uint64_t ms = k1-k0, priv_bytes = privs ? 32UL*ms : 0UL;
+    uint64_t off_at = priv_bytes, first_at = off_at + 8UL*m, sz_at = first_at + 4UL*( ms+1UL ), in_bytes = sz_at + 4UL*m;
+    uint64_t sigs_at = 32UL*ms, codes_at = 96UL*ms, out_bytes = 97UL*ms;
+    if( (err = front_room( e, m*FD_SHRED_CORE_MAX_SZ, in_bytes, out_bytes )) ) return err;
+    uint64_t * h_off   = (uint64_t *)( e->h_fr_in + off_at );
+    uint32_t * h_first = (uint32_t *)( e->h_fr_in + first_at );
+    uint32_t * h_sz    = (uint32_t *)( e->h_fr_in + sz_at );
+    if( privs ) memcpy( e->h_fr_in, privs + 32UL*k0, priv_bytes );
+    uint64_t pos = 0UL, i = 0UL;
+    for( uint64_t k=k0; k<k1; k++ ) {
+      uint64_t first = set_first[k], last = set_first[k+1UL];
+      uint64_t cnt = ( first<=last && last<=n && last-first<=FD_FEC_CORE_CNT_MAX ) ? last-first : 0UL;
+      h_first[ k-k0 ] = (uint32_t)i;
+      for( uint64_t j=first; j<first+cnt; j++, i++ ) {
+        uint64_t cp = shred_sz[j]<=FD_SHRED_CORE_MAX_SZ ? shred_sz[j] : FD_SHRED_CORE_MAX_SZ;
+        if( cp ) memcpy( e->h_msgs + pos, shreds + shred_off[j], cp );
+        h_off[i] = pos;
+        h_sz [i] = shred_sz[j];
+        pos += cp;
+      }
+    }
+    h_first[ ms ] = (uint32_t)i;
+    if( (err = grow_dev( &e->d_fr_work, &e->fr_work_cap, FD_ED25519_HIP_FEC_WORK_BYTES( m, ms ) )) ) return err;
+    if( (err = front_upload( e, pos, in_bytes, st )) ) return err;
+    err = fd_ed25519_hip_fec_seal_dev( e, m, e->d_msgs, (unsigned long const *)( e->d_fr_in + off_at ),
+                                       (unsigned int const *)( e->d_fr_in + sz_at ), ms,
+                                       (unsigned int const *)( e->d_fr_in + first_at ), privs ? e->d_fr_in : NULL,
+                                       e->d_fr_work, (signed char *)( e->d_fr_out + codes_at ), e->d_fr_out,
+                                       privs ? e->d_fr_out + sigs_at : NULL, st );
+    if( err ) return err;
+    if( pos ) HIPCHK( hipMemcpyAsync( e->h_msgs, e->d_msgs, pos, hipMemcpyDeviceToHost, st ), "D2H sealed shreds" );
+    if( (err = front_download( e, out_bytes, st )) ) return err;
+    memcpy( set_out + k0, e->h_fr_out + codes_at, ms );
+    if( roots ) memcpy( roots + 32UL*k0, e->h_fr_out, 32UL*ms );
+    if( sigs )  memcpy( sigs  + 64UL*k0, e->h_fr_out + sigs_at, 64UL*ms );
+    for( uint64_t k=k0; k<k1; k++ ) {
+      if( set_out[k] ) continue;                      /* rule 6 */
+      uint64_t first = set_first[k], cnt = set_first[k+1UL]-first, depth = fd_fec_core_depth( (unsigned)cnt );
+      for( uint64_t j=0UL; j<cnt; j++ ) {
+        unsigned char *       dst = shreds + shred_off[ first+j ];
+        unsigned char const * src = e->h_msgs + h_off[ h_first[ k-k0 ]+j ];
+        uint64_t proof_at = ( ( src[ 0x40 ] & 0xf0 )==0x80 ? FD_SHRED_CORE_MIN_SZ : FD_SHRED_CORE_MAX_SZ ) - 20UL*depth;
+        if( privs ) memcpy( dst, src, 64UL );
+        memcpy( dst + proof_at, src + proof_at, 20UL*depth );
+      }
+    }
+    k0 = k1;
+  }
+  return FD_ED25519_HIP_OK;
+}

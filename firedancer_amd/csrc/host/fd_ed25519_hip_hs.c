@@ -1,8 +1,8 @@
 /* fd_ed25519_hip_hs.c -- one host-scalar launch (fd_ed25519_hip_internal.h):
    the block the calling thread fills and dsm16 / dsm16s read in place, the
    order of its launches and writes, and the host's copy of
-   batch_single_msg's combine rule.  The drop-in (fd_ed25519_hip_engine.c
-   dropin_run) and the verify tile's pipe (fd_ed25519_hip_tile.c
+   batch_single_msg's combine rule.  The drop-in (fd_ed25519_hip_dropin.c
+   dropin_launch_hs) and the verify tile's pipe (fd_ed25519_hip_tile.c
    pipe_submit_hs) each walk their own inputs through it.
 
    The order that must hold: the launch that waits goes before any host

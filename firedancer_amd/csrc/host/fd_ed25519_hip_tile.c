@@ -1,51 +1,28 @@
 /* fd_ed25519_hip_tile.c -- host runtime between Firedancer's verify tile
    and the GPU engine (include/fd_ed25519_hip_tile.h): the asynchronous
    pipe, the transaction parser and tcache the verify tile needs, the
-   batched verify-tile core, a tango-style ring for the latency mode, and
-   the multi-GPU pool with one feeder thread per device.  Plain C11 +
-   pthreads over the HIP runtime. */
+   batched verify-tile core (vtile), a tango-style ring for the latency
+   mode, and the verify service.  Plain C11 + pthreads over the HIP
+   runtime and the engine's public API.
+
+   One file on purpose: the vtile and the service write members of the
+   pipe's slot (pipe_slot_t: ext_src, warming, seq), so a file per layer
+   would need a struct header per layer, more machinery than it saves.
+   The multi-GPU pool, which touches none of this, is
+   fd_ed25519_hip_pool.c. */
 
 #define _GNU_SOURCE
+#include "fd_ed25519_hip_host.h"
 #include "../../../include/fd_ed25519_hip_tile.h"
 #include "../fd_ed25519_hip_internal.h"
 
-#include <hip/hip_runtime_api.h>
 #include <pthread.h>
 #include <sched.h>
 #include <stdatomic.h>
-#ifdef FD_ED25519_HIP_AB_SERVICE_PROFILE
-#include <x86intrin.h>
-#endif
 #include <stdint.h>
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
-#include <time.h>
-
-/* engine.c's error buffer is thread-local there; this file reports through
-   its own setter so that fd_ed25519_hip_last_error() sees both */
-extern char const * fd_ed25519_hip_last_error( void );
-void fd_ed25519_hip_private_set_error( char const * msg );
-
-static double
-now_s( void ) {
-  struct timespec ts;
-  clock_gettime( CLOCK_MONOTONIC, &ts );
-  return (double)ts.tv_sec + 1e-9 * (double)ts.tv_nsec;
-}
-
-static int
-tile_fail( char const * what, hipError_t err ) {
-  char buf[ 256 ];
-  snprintf( buf, sizeof(buf), "%s: %s (%d)", what, hipGetErrorString( err ), (int)err );
-  fd_ed25519_hip_private_set_error( buf );
-  return FD_ED25519_HIP_ERR_HIP - (int)err;
-}
-
-#define TCHK( call, what ) do {                       \
-    hipError_t _e = (call);                           \
-    if( _e!=hipSuccess ) return tile_fail( what, _e ); \
-  } while(0)
 
 unsigned
 fd_ed25519_hip_abi_version( void ) {
@@ -57,12 +34,11 @@ fd_ed25519_hip_abi_check( unsigned version, unsigned long slot_sz, unsigned long
                           unsigned long vservice_stats_sz ) {
   if( version!=FD_ED25519_HIP_ABI_VERSION || slot_sz!=sizeof(fd_ed25519_hip_slot_t) ||
       info_sz!=sizeof(fd_ed25519_hip_info_t) || vservice_stats_sz!=sizeof(fd_ed25519_hip_vservice_stats_t) ) {
-    char buf[ 200 ];
-    snprintf( buf, sizeof(buf), "ABI mismatch: caller v%u (%lu, %lu, %lu), library v%u (%lu, %lu, %lu)",
-              version, slot_sz, info_sz, vservice_stats_sz, FD_ED25519_HIP_ABI_VERSION,
-              (unsigned long)sizeof(fd_ed25519_hip_slot_t), (unsigned long)sizeof(fd_ed25519_hip_info_t),
-              (unsigned long)sizeof(fd_ed25519_hip_vservice_stats_t) );
-    fd_ed25519_hip_private_set_error( buf );
+    fd_ed25519_hip_private_set_errorf( "ABI mismatch: caller v%u (%lu, %lu, %lu), library v%u (%lu, %lu, %lu)",
+                                       version, slot_sz, info_sz, vservice_stats_sz, FD_ED25519_HIP_ABI_VERSION,
+                                       (unsigned long)sizeof(fd_ed25519_hip_slot_t),
+                                       (unsigned long)sizeof(fd_ed25519_hip_info_t),
+                                       (unsigned long)sizeof(fd_ed25519_hip_vservice_stats_t) );
     return FD_ED25519_HIP_ERR_INVAL;
   }
   return FD_ED25519_HIP_OK;
@@ -78,18 +54,6 @@ fd_ed25519_hip_abi_check( unsigned version, unsigned long slot_sz, unsigned long
    partial-line fills; the staging ring is megabytes, far out of L2), and
    the few bytes of padding per payload cost the link nothing that matters. */
 #define STAGE_ALIGN( off ) ( ( (off) + 63UL ) & ~63UL )
-
-
-#ifdef FD_ED25519_HIP_AB_SERVICE_PROFILE
-/* A/B build only: host cycles inside each part of a batch submit
-   (pf_sub_launch, for a host-scalar batch: the module's launching steps,
-   fd_ed25519_hip_private_hs_begin and hs_end, whose go-word stores it then
-   counts too) */
-static __thread unsigned long long pf_sub_h2d, pf_sub_launch, pf_sub_d2h, pf_sub_n, pf_sub_wait;
-#define PF_SUB( acc, stmt ) do { unsigned long long c_ = __rdtsc(); stmt; acc += __rdtsc() - c_; } while(0)
-#else
-#define PF_SUB( acc, stmt ) do { stmt; } while(0)
-#endif
 
 #ifdef FD_ED25519_HIP_AB_STAGE_TRACE
 /* A/B build only (tools/stage_trace_probe.py): per batch, the host time of
@@ -312,18 +276,18 @@ pipe_slot_init( pipe_slot_t * s, int device, unsigned long sig_cap, unsigned lon
   /* codes out: [sig_out | txn_out | trailers (64 B per transaction)] */
   s->out_trl = (sig_cap + tc + 63UL) & ~63UL;
   unsigned long out_sz = s->out_trl + 64UL*tc;
-  TCHK( hipHostMalloc( (void **)&s->h_in,   in_sz,  hipHostMallocDefault ), "hipHostMalloc" );
-  TCHK( hipHostMalloc( (void **)&s->h_outb, out_sz, hipHostMallocCoherent ), "hipHostMalloc" );
-  TCHK( hipMalloc(     (void **)&s->d_in,   in_sz                        ), "hipMalloc" );
-  TCHK( hipHostGetDevicePointer( (void **)&s->h_in_dev, s->h_in, 0U ), "hipHostGetDevicePointer" );
-  TCHK( hipHostGetDevicePointer( (void **)&s->h_outb_dev, s->h_outb, 0U ), "hipHostGetDevicePointer" );
+  HIPCHK( hipHostMalloc( (void **)&s->h_in,   in_sz,  hipHostMallocDefault ), "hipHostMalloc" );
+  HIPCHK( hipHostMalloc( (void **)&s->h_outb, out_sz, hipHostMallocCoherent ), "hipHostMalloc" );
+  HIPCHK( hipMalloc(     (void **)&s->d_in,   in_sz                        ), "hipMalloc" );
+  HIPCHK( hipHostGetDevicePointer( (void **)&s->h_in_dev, s->h_in, 0U ), "hipHostGetDevicePointer" );
+  HIPCHK( hipHostGetDevicePointer( (void **)&s->h_outb_dev, s->h_outb, 0U ), "hipHostGetDevicePointer" );
   /* the device-decode layout at the work arrays' stride (no points), or the
      host-decode one at the small stride: room for the larger */
   unsigned long hs_dev = fd_ed25519_hip_private_hs_bytes( sig_cap, 0 );
   unsigned long hs_host = fd_ed25519_hip_private_hs_bytes( FD_ED25519_HS_STRIDE, 1 );
-  TCHK( hipHostMalloc( (void **)&s->h_hs, hs_dev>hs_host ? hs_dev : hs_host, hipHostMallocCoherent ), "hipHostMalloc" );
-  TCHK( hipHostGetDevicePointer( (void **)&s->h_hs_dev, s->h_hs, 0U ), "hipHostGetDevicePointer" );
-  TCHK( hipMalloc(     (void **)&s->d_outb, out_sz                       ), "hipMalloc" );
+  HIPCHK( hipHostMalloc( (void **)&s->h_hs, hs_dev>hs_host ? hs_dev : hs_host, hipHostMallocCoherent ), "hipHostMalloc" );
+  HIPCHK( hipHostGetDevicePointer( (void **)&s->h_hs_dev, s->h_hs, 0U ), "hipHostGetDevicePointer" );
+  HIPCHK( hipMalloc(     (void **)&s->d_outb, out_sz                       ), "hipMalloc" );
   p->sigs        = s->h_in + o_sigs;                   s->d_sigs   = s->d_in + o_sigs;
   p->pubs        = s->h_in + o_pubs;                   s->d_pubs   = s->d_in + o_pubs;
   p->msg_off     = (unsigned long *)(s->h_in + o_off); s->d_off    = (unsigned long *)(s->d_in + o_off);
@@ -334,12 +298,12 @@ pipe_slot_init( pipe_slot_t * s, int device, unsigned long sig_cap, unsigned lon
   p->sig_out     = s->h_outb;                          s->d_out    = s->d_outb;
   p->txn_out     = s->h_outb + sig_cap;                s->d_tout   = s->d_outb + sig_cap;
   p->txn_trailer = (unsigned char *)s->h_outb + s->out_trl;  s->d_trailer = (unsigned char *)s->d_outb + s->out_trl;
-  TCHK( hipMalloc( (void **)&s->d_soff, 8UL*sig_cap ), "hipMalloc" );
-  TCHK( hipMalloc( (void **)&s->d_ssz,  4UL*sig_cap ), "hipMalloc" );
-  TCHK( hipMalloc( (void **)&s->d_pok,  tc          ), "hipMalloc" );
+  HIPCHK( hipMalloc( (void **)&s->d_soff, 8UL*sig_cap ), "hipMalloc" );
+  HIPCHK( hipMalloc( (void **)&s->d_ssz,  4UL*sig_cap ), "hipMalloc" );
+  HIPCHK( hipMalloc( (void **)&s->d_pok,  tc          ), "hipMalloc" );
   s->dev_bytes = in_sz + out_sz + 12UL*sig_cap + tc;
-  TCHK( hipEventCreateWithFlags( &s->ev, hipEventDisableTiming ), "hipEventCreate" );
-  TCHK( hipEventCreateWithFlags( &s->ev_h2d, hipEventDisableTiming ), "hipEventCreate" );
+  HIPCHK( hipEventCreateWithFlags( &s->ev, hipEventDisableTiming ), "hipEventCreate" );
+  HIPCHK( hipEventCreateWithFlags( &s->ev_h2d, hipEventDisableTiming ), "hipEventCreate" );
   s->state = SLOT_FREE;
   return FD_ED25519_HIP_OK;
 }
@@ -355,7 +319,7 @@ fd_ed25519_hip_pipe_new( int device, unsigned slot_cnt, unsigned long sig_cap, u
   if( !pipe ) { fd_ed25519_hip_private_set_error( "pipe_new: calloc failed" ); return NULL; }
   pipe->device   = device;
   pipe->slot_cnt = slot_cnt;
-  if( hipSetDevice( device )!=hipSuccess ) { tile_fail( "hipSetDevice", hipErrorInvalidDevice ); free( pipe ); return NULL; }
+  if( hipSetDevice( device )!=hipSuccess ) { fd_ed25519_hip_private_hip_fail( hipErrorInvalidDevice, "hipSetDevice" ); free( pipe ); return NULL; }
   for( unsigned i=0U; i<slot_cnt; i++ ) {
     if( pipe_slot_init( &pipe->slot[i], device, sig_cap, msg_cap, txn_cap, flags ) ) {
       fd_ed25519_hip_pipe_delete( pipe );
@@ -426,9 +390,7 @@ slot_h2d( fd_ed25519_hip_pipe_t * pipe, pipe_slot_t * s, hipStream_t st, unsigne
           unsigned long txn_cnt, unsigned long msg_bytes ) {
   int ordered = sig_cnt>FD_ED25519_HIP_PIPE_H2D_ORDER_MIN;
   if( ordered && pipe->h2d_tail ) {
-    hipError_t we_;
-    PF_SUB( pf_sub_wait, we_ = hipStreamWaitEvent( st, pipe->h2d_tail, 0U ) );
-    TCHK( we_, "hipStreamWaitEvent(h2d)" );
+    HIPCHK( hipStreamWaitEvent( st, pipe->h2d_tail, 0U ), "hipStreamWaitEvent(h2d)" );
   }
   h2d_span_t sp[ 9 ];
   unsigned k = slot_h2d_spans( s, sig_cnt, txn_cnt, s->ext_src[0] ? 0UL : msg_bytes, sp );
@@ -444,10 +406,10 @@ slot_h2d( fd_ed25519_hip_pipe_t * pipe, pipe_slot_t * s, hipStream_t st, unsigne
       pp.src[ pp.cnt ] = sp[ i ].dev; pp.dst[ pp.cnt ] = sp[ i ].dst; pp.n[ pp.cnt ] = sp[ i ].n; pp.cnt++;
     }
     int le = fd_ed25519_hip_launch_pull( &pp, st );
-    if( le ) return tile_fail( "H2D pull launch", (hipError_t)le );
+    if( le ) return fd_ed25519_hip_private_hip_fail( (hipError_t)le, "H2D pull launch" );
   }
   if( ordered ) {
-    TCHK( hipEventRecord( s->ev_h2d, st ), "hipEventRecord(h2d)" );
+    HIPCHK( hipEventRecord( s->ev_h2d, st ), "hipEventRecord(h2d)" );
     pipe->h2d_tail = s->ev_h2d;
   }
   return FD_ED25519_HIP_OK;
@@ -467,7 +429,7 @@ slot_d2h( pipe_slot_t * s, hipStream_t st, unsigned long sig_cnt, unsigned long 
   memset( &pp, 0, sizeof(pp) );
   pp.src[0] = (unsigned char const *)s->d_outb; pp.dst[0] = s->h_outb_dev; pp.n[0] = n; pp.cnt = 1U;
   int le = fd_ed25519_hip_launch_pull( &pp, st );
-  if( le ) return tile_fail( "D2H push launch", (hipError_t)le );
+  if( le ) return fd_ed25519_hip_private_hip_fail( (hipError_t)le, "D2H push launch" );
   return FD_ED25519_HIP_OK;
 }
 
@@ -507,6 +469,19 @@ slot_check( fd_ed25519_hip_slot_t const * slot, unsigned long sig_cnt, unsigned 
   return FD_ED25519_HIP_OK;
 }
 
+/* what every submit ends with, its last launch enqueued: the slot's event
+   recorded behind it, the slot busy and counted in flight */
+static int
+pipe_submitted( fd_ed25519_hip_pipe_t * pipe, pipe_slot_t * s, hipStream_t st ) {
+  HIPCHK( hipEventRecord( s->ev, st ), "hipEventRecord" );
+#ifdef FD_ED25519_HIP_AB_STAGE_TRACE
+  s->t_enq = now_s(); s->in_flight0 = pipe->in_flight;
+#endif
+  s->state = SLOT_BUSY;
+  pipe->in_flight++;
+  return FD_ED25519_HIP_OK;
+}
+
 /* A host-scalar batch (PIPE_HS_MAX above; the sequence is
    host/fd_ed25519_hip_hs.c's): the decompressions launched
    first, the scalars computed meanwhile, then dsm16 writing the signature
@@ -529,8 +504,8 @@ pipe_submit_hs( fd_ed25519_hip_pipe_t * pipe, pipe_slot_t * s, hipStream_t st ) 
   fd_ed25519_hip_hs_t hb;
   fd_ed25519_hip_private_hs_init( &hb, s->h_hs, hd ? FD_ED25519_HS_STRIDE : cap, hd, n, split,
                                   !fd_ed25519_hip_private_codes_portable( s->eng ) );
-  PF_SUB( pf_sub_launch, err = fd_ed25519_hip_private_hs_begin( &hb, s->eng, s->h_hs_dev, s->h_in_dev + o_sigs,
-                                                                s->h_in_dev + o_pubs, (signed char *)s->h_outb_dev, st ) );
+  err = fd_ed25519_hip_private_hs_begin( &hb, s->eng, s->h_hs_dev, s->h_in_dev + o_sigs, s->h_in_dev + o_pubs,
+                                         (signed char *)s->h_outb_dev, st );
   if( err ) return err;
   int all = 1, dbits = fd_ed25519_hip_private_half_dbits( s->eng );
   unsigned char const * enc[ 2UL*FD_ED25519_HS_DECODE_MAX ];   /* A and R of each signature, side by side */
@@ -540,17 +515,12 @@ pipe_submit_hs( fd_ed25519_hip_pipe_t * pipe, pipe_slot_t * s, hipStream_t st ) 
     if( hd ) { enc[ 2UL*i ] = slot->pubs + 32UL*i; enc[ 2UL*i+1UL ] = slot->sigs + 64UL*i; }
   }
   if( all && hd ) fd_ed25519_hip_private_hs_points( &hb, enc );
-  PF_SUB( pf_sub_launch, err = fd_ed25519_hip_private_hs_end( &hb, all ) );
+  err = fd_ed25519_hip_private_hs_end( &hb, all );
   if( err ) return err;
   if( !all ) return 0;
   s->host_combine = slot->txn_cnt ? 1 : 0;
-  TCHK( hipEventRecord( s->ev, st ), "hipEventRecord" );
-#ifdef FD_ED25519_HIP_AB_STAGE_TRACE
-  s->t_enq = now_s(); s->in_flight0 = pipe->in_flight;
-#endif
-  s->state = SLOT_BUSY;
-  pipe->in_flight++;
-  return 1;
+  err = pipe_submitted( pipe, s, st );
+  return err ? err : 1;
 }
 
 /* batch_single_msg's rule per transaction of a host-scalar batch */
@@ -568,7 +538,7 @@ fd_ed25519_hip_pipe_submit( fd_ed25519_hip_pipe_t * pipe, fd_ed25519_hip_slot_t 
   if( s->state!=SLOT_FILL || sig_cnt>slot->sig_cap || msg_bytes>slot->msg_cap || txn_cnt>slot->txn_cap )
     return FD_ED25519_HIP_ERR_INVAL;
   if( slot_check( slot, sig_cnt, msg_bytes, txn_cnt ) ) return FD_ED25519_HIP_ERR_INVAL;
-  TCHK( hipSetDevice( pipe->device ), "hipSetDevice" );
+  HIPCHK( hipSetDevice( pipe->device ), "hipSetDevice" );
   hipStream_t st = (hipStream_t)fd_ed25519_hip_engine_stream( s->eng );
   slot->sig_cnt = sig_cnt; slot->msg_bytes = msg_bytes; slot->txn_cnt = txn_cnt;
   slot->seq = pipe->seq++;
@@ -580,7 +550,7 @@ fd_ed25519_hip_pipe_submit( fd_ed25519_hip_pipe_t * pipe, fd_ed25519_hip_slot_t 
     if( err<0 ) return err;
     if( err==1 ) return FD_ED25519_HIP_OK;   /* 0: a signature without a half-size pair, the device's own path below */
   }
-  PF_SUB( pf_sub_h2d, err = slot_h2d( pipe, s, st, sig_cnt, txn_cnt, msg_bytes ) );
+  err = slot_h2d( pipe, s, st, sig_cnt, txn_cnt, msg_bytes );
   if( err ) return err;
 #ifdef FD_ED25519_HIP_HOST_FAULT
   /* test build only (tests/test_gpu_service_fault.py): the stream's third
@@ -590,8 +560,7 @@ fd_ed25519_hip_pipe_submit( fd_ed25519_hip_pipe_t * pipe, fd_ed25519_hip_slot_t 
   if( slot->seq==2UL && !pipe->warming ) {
     char const * stall = getenv( "FD_ED25519_HIP_FAULT_STALL_MS" );
     if( stall && *stall ) {
-      err = fd_ed25519_hip_launch_stall( (unsigned)strtoul( stall, NULL, 10 ), st );
-      if( err ) return tile_fail( "stall launch", (hipError_t)err );
+      HIPCHK( (hipError_t)fd_ed25519_hip_launch_stall( (unsigned)strtoul( stall, NULL, 10 ), st ), "stall launch" );
     } else {
       fd_ed25519_hip_private_set_error( "pipe: injected launch failure (fault-injection build)" );
       return FD_ED25519_HIP_ERR_HIP - (int)hipErrorLaunchFailure;
@@ -599,27 +568,16 @@ fd_ed25519_hip_pipe_submit( fd_ed25519_hip_pipe_t * pipe, fd_ed25519_hip_slot_t 
   }
 #endif
   if( sig_cnt ) {
-    PF_SUB( pf_sub_launch, err = fd_ed25519_hip_verify_dev( s->eng, sig_cnt, s->d_msgs, s->d_off, s->d_sz, s->d_sigs,
-                                                             s->d_pubs, s->d_out, st ) );
+    err = fd_ed25519_hip_verify_dev( s->eng, sig_cnt, s->d_msgs, s->d_off, s->d_sz, s->d_sigs, s->d_pubs, s->d_out, st );
     if( err ) return err;
   }
   if( txn_cnt ) {
-    PF_SUB( pf_sub_launch, err = fd_ed25519_hip_txn_combine_dev( s->eng, txn_cnt, s->d_out, s->d_tfirst, s->d_tcnt,
-                                                                 s->d_tout, st ) );
+    err = fd_ed25519_hip_txn_combine_dev( s->eng, txn_cnt, s->d_out, s->d_tfirst, s->d_tcnt, s->d_tout, st );
     if( err ) return err;
   }
-  PF_SUB( pf_sub_d2h, err = slot_d2h( s, st, sig_cnt, txn_cnt, 0 ) );
+  err = slot_d2h( s, st, sig_cnt, txn_cnt, 0 );
   if( err ) return err;
-#ifdef FD_ED25519_HIP_AB_SERVICE_PROFILE
-  pf_sub_n++;
-#endif
-  TCHK( hipEventRecord( s->ev, st ), "hipEventRecord" );
-#ifdef FD_ED25519_HIP_AB_STAGE_TRACE
-  s->t_enq = now_s(); s->in_flight0 = pipe->in_flight;
-#endif
-  s->state = SLOT_BUSY;
-  pipe->in_flight++;
-  return FD_ED25519_HIP_OK;
+  return pipe_submitted( pipe, s, st );
 }
 
 int
@@ -645,7 +603,7 @@ fd_ed25519_hip_pipe_submit_txns( fd_ed25519_hip_pipe_t * pipe, fd_ed25519_hip_sl
     if( c>=1U && c<=16U ) slots += c;
   }
   if( slots>slot->sig_cap ) return FD_ED25519_HIP_ERR_INVAL;
-  TCHK( hipSetDevice( pipe->device ), "hipSetDevice" );
+  HIPCHK( hipSetDevice( pipe->device ), "hipSetDevice" );
   hipStream_t st = (hipStream_t)fd_ed25519_hip_engine_stream( s->eng );
   slot->sig_cnt = slots; slot->msg_bytes = payload_bytes; slot->txn_cnt = txn_cnt;
   slot->seq = pipe->seq++;
@@ -655,36 +613,23 @@ fd_ed25519_hip_pipe_submit_txns( fd_ed25519_hip_pipe_t * pipe, fd_ed25519_hip_sl
     /* the per-transaction offsets / sizes travel in msg_off / msg_sz; the
        device writes the per-signature ones (and the signatures and keys)
        into arrays of its own */
-    int err;
-    PF_SUB( pf_sub_h2d, err = slot_h2d( pipe, s, st, 0UL, txn_cnt, payload_bytes ) );
+    int err = slot_h2d( pipe, s, st, 0UL, txn_cnt, payload_bytes );
     if( err ) return err;
     fd_ed25519_txn_stage_params_t sp;
     sp.payloads = s->d_msgs; sp.pay_off = s->d_off; sp.pay_sz = s->d_sz; sp.txn_first = s->d_tfirst;
     sp.txn_cnt = s->d_tcnt; sp.ntxn = txn_cnt; sp.sigs = s->d_sigs; sp.pubs = s->d_pubs; sp.msg_off = s->d_soff;
     sp.msg_sz = s->d_ssz; sp.parse_ok = s->d_pok; sp.trailer = s->d_trailer;
-    PF_SUB( pf_sub_launch, err = fd_ed25519_hip_launch_txn_stage( &sp, st ) );
-    if( err ) return tile_fail( "txn_stage launch", (hipError_t)err );
+    HIPCHK( (hipError_t)fd_ed25519_hip_launch_txn_stage( &sp, st ), "txn_stage launch" );
     if( slots ) {
-        PF_SUB( pf_sub_launch, err = fd_ed25519_hip_verify_dev( s->eng, slots, s->d_msgs, s->d_soff, s->d_ssz, s->d_sigs,
-                                                               s->d_pubs, s->d_out, st ) );
+      err = fd_ed25519_hip_verify_dev( s->eng, slots, s->d_msgs, s->d_soff, s->d_ssz, s->d_sigs, s->d_pubs, s->d_out, st );
       if( err ) return err;
     }
-    PF_SUB( pf_sub_launch, err = fd_ed25519_hip_launch_txn_finish( s->d_out, s->d_tfirst, s->d_tcnt, s->d_pok, s->d_tout,
-                                                                   txn_cnt, st ) );
-    if( err ) return tile_fail( "txn_finish launch", (hipError_t)err );
-    PF_SUB( pf_sub_d2h, err = slot_d2h( s, st, slots, txn_cnt, 1 ) );
+    HIPCHK( (hipError_t)fd_ed25519_hip_launch_txn_finish( s->d_out, s->d_tfirst, s->d_tcnt, s->d_pok, s->d_tout, txn_cnt, st ),
+            "txn_finish launch" );
+    err = slot_d2h( s, st, slots, txn_cnt, 1 );
     if( err ) return err;
-#ifdef FD_ED25519_HIP_AB_SERVICE_PROFILE
-    pf_sub_n++;
-#endif
   }
-  TCHK( hipEventRecord( s->ev, st ), "hipEventRecord" );
-#ifdef FD_ED25519_HIP_AB_STAGE_TRACE
-  s->t_enq = now_s(); s->in_flight0 = pipe->in_flight;
-#endif
-  s->state = SLOT_BUSY;
-  pipe->in_flight++;
-  return FD_ED25519_HIP_OK;
+  return pipe_submitted( pipe, s, st );
 }
 
 fd_ed25519_hip_slot_t *
@@ -699,7 +644,7 @@ fd_ed25519_hip_pipe_poll( fd_ed25519_hip_pipe_t * pipe, int wait ) {
        (the verify service marks its links failed and stops) */
     char what[ 64 ];
     snprintf( what, sizeof(what), "batch %lu failed on the GPU", s->pub.seq );
-    if( !pipe->err ) pipe->err = tile_fail( what, e );
+    if( !pipe->err ) pipe->err = fd_ed25519_hip_private_hip_fail( e, what );
     return NULL;
   }
   s->pub.t_done = now_s();
@@ -1142,30 +1087,15 @@ vt_resolve( fd_ed25519_hip_vtile_t * vt, fd_ed25519_hip_slot_t * s ) {
   vt_advance( vt );
 }
 
-#ifdef FD_ED25519_HIP_AB_SERVICE_PROFILE
-static __thread unsigned long long vt_wait_cycles, vt_resolve_cycles, vt_blocks;   /* A/B build only */
-static __thread unsigned long long vt_submit_cycles, vt_submits, vt_rtt_n;
-static __thread double             vt_rtt_s, vt_rtt_max_s;
-#endif
 
 static int
 vt_drain_one( fd_ed25519_hip_vtile_t * vt, int wait ) {
   if( vt->err ) return 0;
-#ifdef FD_ED25519_HIP_AB_SERVICE_PROFILE
-  unsigned long long w0 = __rdtsc();
-#endif
   fd_ed25519_hip_slot_t * s = fd_ed25519_hip_pipe_poll( vt->pipe, wait );
-#ifdef FD_ED25519_HIP_AB_SERVICE_PROFILE
-  unsigned long long w1 = __rdtsc();
-  if( wait ) { vt_wait_cycles += w1 - w0; vt_blocks++; }
-#endif
   if( !s ) {
     if( fd_ed25519_hip_pipe_error( vt->pipe ) ) vt->err = fd_ed25519_hip_pipe_error( vt->pipe );
     return 0;
   }
-#ifdef FD_ED25519_HIP_AB_SERVICE_PROFILE
-  { double rt = s->t_done - s->t_submit; vt_rtt_s += rt; vt_rtt_n++; if( rt>vt_rtt_max_s ) vt_rtt_max_s = rt; }
-#endif
   vt_resolve( vt, s );
 #ifdef FD_ED25519_HIP_AB_STAGE_TRACE
   if( stage_cnt<STAGE_TRACE_MAX ) {
@@ -1177,9 +1107,6 @@ vt_drain_one( fd_ed25519_hip_vtile_t * vt, int wait ) {
   }
 #endif
   fd_ed25519_hip_pipe_release( vt->pipe, s );
-#ifdef FD_ED25519_HIP_AB_SERVICE_PROFILE
-  vt_resolve_cycles += __rdtsc() - w1;
-#endif
   return 1;
 }
 
@@ -1197,14 +1124,8 @@ vt_submit_open( fd_ed25519_hip_vtile_t * vt ) {
     }
     vt->zc_seg = 0;
   }
-#ifdef FD_ED25519_HIP_AB_SERVICE_PROFILE
-  unsigned long long sc0 = __rdtsc();
-#endif
   int err = vt->gpu_parse ? fd_ed25519_hip_pipe_submit_txns( vt->pipe, s, s->txn_cnt, s->msg_bytes )
                           : fd_ed25519_hip_pipe_submit( vt->pipe, s, s->sig_cnt, s->msg_bytes, s->txn_cnt );
-#ifdef FD_ED25519_HIP_AB_SERVICE_PROFILE
-  vt_submit_cycles += __rdtsc() - sc0; vt_submits++;
-#endif
   if( err ) {   /* a launch failed: the batch's transactions have no verdicts, and the vtile stops */
     vt->err = err;
     return 0;
@@ -1230,10 +1151,8 @@ vt_wait_oldest( fd_ed25519_hip_vtile_t * vt ) {
       int r = vt->idle( vt->idle_ctx );
       if( r ) { vt->err = r; return 0; }
       if( vt->hang_s>0.0 && now_s() - t0>vt->hang_s ) {
-        char buf[ 128 ];
-        snprintf( buf, sizeof(buf), "vtile: batch %lu did not complete within %.1f s (GPU hang)",
-                  vt->pipe->seq - fd_ed25519_hip_pipe_in_flight( vt->pipe ), vt->hang_s );
-        fd_ed25519_hip_private_set_error( buf );
+        fd_ed25519_hip_private_set_errorf( "vtile: batch %lu did not complete within %.1f s (GPU hang)",
+                                           vt->pipe->seq - fd_ed25519_hip_pipe_in_flight( vt->pipe ), vt->hang_s );
         vt->err = FD_ED25519_HIP_ERR_TIMEOUT;
         return 0;
       }
@@ -2014,16 +1933,8 @@ typedef struct {
   unsigned long                     txns, pass;
   int                               eos, idle, live;
   char                              errmsg[ 256 ];   /* last_error of a device-wide end (it is per thread) */
-#ifdef FD_ED25519_HIP_AB_SERVICE_PROFILE
-  unsigned long long                pf_t[ 5 ], pf_idle, pf_pass, pf_cons;
-#endif
 } vsvc_t;
 
-#ifdef FD_ED25519_HIP_AB_SERVICE_PROFILE
-#define PF_MARK( i ) do { pf_n = __rdtsc(); S->pf_t[ i ] += pf_n - pf_c; pf_c = pf_n; } while(0)
-#else
-#define PF_MARK( i ) do {} while(0)
-#endif
 
 /* the pair ends with rc (0: EOS answered): both links marked failed with a
    failure code, the sibling pairs stopped when the cause is the device's
@@ -2063,18 +1974,6 @@ vsvc_end( vsvc_t * S, int rc, int local ) {
     S->stats->shared_device_bytes = fd_ed25519_hip_shared_device_bytes( S->device );
     S->stats->end_code     = rc;
   }
-#ifdef FD_ED25519_HIP_AB_SERVICE_PROFILE
-  double d = (double)( S->txns + 1UL );
-  fprintf( stderr, "vservice profile: %lu txns, %llu passes (%llu idle); cycles per txn: status %.0f publish %.0f "
-           "poll %.0f consume+frag %.0f (of which consume %.0f) flush+pause %.0f; %llu batches: submit %.0f cycles each, "
-           "round trip avg %.3f ms max %.3f ms; submit parts per batch: h2d %.0f (wait %.0f) launches %.0f d2h %.0f\n",
-           S->txns, S->pf_pass, S->pf_idle, (double)S->pf_t[0]/d, (double)S->pf_t[1]/d, (double)S->pf_t[2]/d,
-           (double)S->pf_t[3]/d, (double)S->pf_cons/d, (double)S->pf_t[4]/d, vt_submits,
-           (double)vt_submit_cycles/(double)( vt_submits + 1ULL ), 1e3*vt_rtt_s/(double)( vt_rtt_n + 1ULL ),
-           1e3*vt_rtt_max_s, (double)pf_sub_h2d/(double)( pf_sub_n + 1ULL ),
-           (double)pf_sub_wait/(double)( pf_sub_n + 1ULL ), (double)pf_sub_launch/(double)( pf_sub_n + 1ULL ),
-           (double)pf_sub_d2h/(double)( pf_sub_n + 1ULL ) );
-#endif
   free( S->buf ); S->buf = NULL;
   if( hung ) {   /* nothing that waits on the device: left for the process exit */
     S->vt = NULL; S->reg = NULL; S->live = 0;
@@ -2120,11 +2019,11 @@ vsvc_open( vsvc_t * S, int device, unsigned slot_cnt, unsigned long batch_sigs, 
     unsigned long map_sz;
     void * m = fd_ed25519_hip_shlink_mapping( in, &map_sz );
     hipError_t he = hipHostRegister( m, map_sz, hipHostRegisterPortable | hipHostRegisterMapped );
-    if( he!=hipSuccess ) { int rc = tile_fail( "hipHostRegister(txn link)", he ); vsvc_end( S, rc, 0 ); return rc; }
+    if( he!=hipSuccess ) { int rc = fd_ed25519_hip_private_hip_fail( he, "hipHostRegister(txn link)" ); vsvc_end( S, rc, 0 ); return rc; }
     S->reg = m;
     void * m_dev = NULL;
     he = hipHostGetDevicePointer( &m_dev, m, 0U );
-    if( he!=hipSuccess ) { int rc = tile_fail( "hipHostGetDevicePointer(txn link)", he ); vsvc_end( S, rc, 0 ); return rc; }
+    if( he!=hipSuccess ) { int rc = fd_ed25519_hip_private_hip_fail( he, "hipHostGetDevicePointer(txn link)" ); vsvc_end( S, rc, 0 ); return rc; }
     vt->zero_copy = 1;
     vt->gpu_parse = 1;
     vt->zc_base   = fd_ed25519_hip_shlink_dcache( in, &vt->zc_size );
@@ -2151,29 +2050,22 @@ static void
 vsvc_pass( vsvc_t * S ) {
   fd_ed25519_hip_vtile_t * vt = S->vt;
   int rc, local = 1;
-#ifdef FD_ED25519_HIP_AB_SERVICE_PROFILE
-  unsigned long long pf_c = __rdtsc(), pf_n;
-#endif
   /* the liveness pass (a clock read, the peer's header lines) runs every
      16th busy pass and on every idle one: microseconds apart either way */
   if( S->idle || !(++S->pass & 15UL) ) {
     if( (rc = vsvc_check( &S->L, &local )) ) { vsvc_end( S, rc, local ); return; }
     if( vsvc_hung( S ) ) {
-      char msg[ 128 ];
-      snprintf( msg, sizeof(msg), "vservice: batch %lu did not complete within %.1f s (GPU hang)",
-                vt->pipe->seq - vt->pipe->in_flight, S->hang_s );
-      fd_ed25519_hip_private_set_error( msg );
+      fd_ed25519_hip_private_set_errorf( "vservice: batch %lu did not complete within %.1f s (GPU hang)",
+                                         vt->pipe->seq - vt->pipe->in_flight, S->hang_s );
       vsvc_end( S, FD_ED25519_HIP_ERR_TIMEOUT, 0 );
       return;
     }
   }
-  PF_MARK( 0 );
   /* completed batches resolve (in frag order); their verdicts go out as
      far as credits allow: the verdict byte, then (SUCCESS) the trailer of
      the frag the tile publishes (its fd_txn_t and payload_sz, from the
      vtile's arena: the tile has the payload) */
   while( vt_drain_one( vt, 0 ) ) {}
-  PF_MARK( 2 );
   int published = 0;
   for( vrec_t const * r; (r = vt_head( vt )); ) {
     unsigned char * dst = fd_ed25519_hip_shlink_prepare( S->L.out );
@@ -2185,7 +2077,6 @@ vsvc_pass( vsvc_t * S ) {
     vt_pop( vt );
     published = 1;
   }
-  PF_MARK( 1 );
   if( (rc = fd_ed25519_hip_vtile_error( vt )) ) {
     /* a wait the idle hook ended is the hook's cause; any other vtile error the device's */
     vsvc_end( S, rc, rc==S->L.hook_rc ? S->L.hook_local : 0 );
@@ -2225,15 +2116,9 @@ vsvc_pass( vsvc_t * S ) {
   while( !S->eos && !vt->zero_copy && vt_room( vt ) ) {
     unsigned long sz = 0UL, sig = 0UL;
     unsigned int ctl = 0U;
-#ifdef FD_ED25519_HIP_AB_SERVICE_PROFILE
-    unsigned long long c0 = __rdtsc();
-#endif
     /* copied out of the shared dcache first: the tile is not trusted not
        to change it meanwhile */
     int r = fd_ed25519_hip_shlink_consume( S->L.in, S->buf, &sz, &sig, &ctl );
-#ifdef FD_ED25519_HIP_AB_SERVICE_PROFILE
-    S->pf_cons += __rdtsc() - c0;
-#endif
     if( r==1 ) break;
     if( r ) { vsvc_end( S, FD_ED25519_HIP_SHLINK_FAIL_PROTOCOL, 1 ); return; }   /* overrun: the tile ignored credits */
     if( ctl & FD_ED25519_HIP_SHLINK_CTL_EOS ) { S->eos = 1; break; }
@@ -2243,7 +2128,6 @@ vsvc_pass( vsvc_t * S ) {
     S->txns++;
     pulled = 1;
   }
-  PF_MARK( 3 );
   /* `in` drained (or the vtile full): send the open batch if a slot can
      take it (all of it at the end) */
   int flushed = 0;
@@ -2253,13 +2137,7 @@ vsvc_pass( vsvc_t * S ) {
     flushed = 1;
   }
   S->idle = !pulled && !published && !flushed;
-#ifdef FD_ED25519_HIP_AB_SERVICE_PROFILE
-  S->pf_idle += (unsigned long long)S->idle;
-  S->pf_pass++;
-#endif
-  PF_MARK( 4 );
 }
-#undef PF_MARK
 
 typedef struct {
   int                                    device, flags;
@@ -2283,9 +2161,7 @@ vservice_main( void * arg ) {
     CPU_ZERO( &set );
     CPU_SET( j->cpu, &set );
     if( pthread_setaffinity_np( pthread_self(), sizeof(set), &set ) ) {
-      char msg[ 96 ];
-      snprintf( msg, sizeof(msg), "vservice: cannot run a service thread on CPU %d", j->cpu );
-      fd_ed25519_hip_private_set_error( msg );
+      fd_ed25519_hip_private_set_errorf( "vservice: cannot run a service thread on CPU %d", j->cpu );
       for( unsigned k=j->k0; k<j->k1; k++ ) {
         vsvc_t * S = &j->pair[ k ];
         memset( S, 0, sizeof(*S) );
@@ -2399,432 +2275,4 @@ fd_ed25519_hip_vservice_run_links( int device, unsigned slot_cnt, unsigned long 
                                    fd_ed25519_hip_shlink_t * const * in, fd_ed25519_hip_shlink_t * const * out,
                                    unsigned link_cnt, fd_ed25519_hip_vservice_stats_t * stats ) {
   return fd_ed25519_hip_vservice_serve( device, slot_cnt, batch_sigs, flags, in, out, link_cnt, stats, NULL );
-}
-
-/* ======================================================================
-   pool: one feeder thread per device, batches dealt round-robin (batch b
-   to device b % N, the analogue of seq % verify_tile_count,
-   src/app/fdctl/run/tiles/fd_verify.c:46).
-
-   A batch reaches the device without its bytes being touched on the host
-   when the caller's arrays are page-locked (fd_ed25519_hip_host_register,
-   or hipHostMalloc'd): its messages go as one DMA of the byte range they
-   span (the kernels index that range with the caller's own offsets, the
-   device base pointer shifted by the range's start), msg_off / msg_sz /
-   sigs / pubs as one DMA each, and the codes come back by DMA straight
-   into out.  Pageable arrays, or messages scattered so widely that their
-   span is far larger than their bytes, are packed into the slot's pinned
-   staging block first.  Each slot has its own engine (stream and work
-   arrays), so one batch's copies overlap another's kernels; the feeder
-   thread runs on the CPUs of its GPU's NUMA node. */
-
-typedef struct {
-  fd_ed25519_hip_engine_t * eng;
-  hipEvent_t                ev;
-  hipEvent_t                ev_h2d;    /* this slot's last batch has crossed the link */
-  unsigned char *           d_msgs;
-  unsigned long *           d_off;
-  unsigned int *            d_sz;
-  unsigned char *           d_sigs;
-  unsigned char *           d_pubs;
-  signed char *             d_out;
-  unsigned char *           h_stage;   /* pinned: [sigs | pubs | off | sz | msgs], staged batches only (lazy) */
-  signed char *             h_out;     /* pinned codes, when out is pageable (lazy)                           */
-  unsigned long             i0, i1;
-  int                       busy;
-} pool_slot_t;
-
-#define POOL_DEV_MAX  64U
-#define POOL_SLOT_MAX 8U
-
-struct fd_ed25519_hip_pool {
-  unsigned      device_cnt, slot_cnt;
-  unsigned long batch_sigs, msg_cap;
-  int           device[ POOL_DEV_MAX ];
-  pool_slot_t   slot[ POOL_DEV_MAX ][ POOL_SLOT_MAX ];
-};
-
-typedef struct {
-  fd_ed25519_hip_pool_t * pool;
-  unsigned                rank;
-  hipEvent_t              h2d_tail;   /* ev_h2d of the batch submitted last on this device (or NULL) */
-  unsigned long           n;
-  unsigned char const *   msgs;
-  unsigned long const *   msg_off;
-  unsigned int const *    msg_sz;
-  unsigned char const *   sigs;
-  unsigned char const *   pubs;
-  signed char *           out;
-  int                     direct_in, direct_out;   /* caller arrays page-locked */
-  int                     err;
-  char                    errmsg[ 256 ];   /* the feeder's last_error for err (last_error is per thread) */
-  fd_ed25519_hip_pool_stats_t st;
-} pool_job_t;
-
-static int
-host_locked( void const * p ) {
-  if( !p ) return 0;
-  hipPointerAttribute_t a;
-  memset( &a, 0, sizeof(a) );
-  if( hipPointerGetAttributes( &a, p )!=hipSuccess ) { (void)hipGetLastError(); return 0; }
-  return a.type==hipMemoryTypeHost;
-}
-
-int
-fd_ed25519_hip_host_register( void * ptr, unsigned long sz ) {
-  if( !ptr || !sz ) return FD_ED25519_HIP_ERR_INVAL;
-  TCHK( hipHostRegister( ptr, sz, hipHostRegisterPortable | hipHostRegisterMapped ), "hipHostRegister" );
-  return FD_ED25519_HIP_OK;
-}
-
-int
-fd_ed25519_hip_host_unregister( void * ptr ) {
-  if( !ptr ) return FD_ED25519_HIP_ERR_INVAL;
-  TCHK( hipHostUnregister( ptr ), "hipHostUnregister" );
-  return FD_ED25519_HIP_OK;
-}
-
-void *
-fd_ed25519_hip_host_alloc( unsigned long sz ) {
-  void * p = NULL;
-  hipError_t e = hipHostMalloc( &p, sz ? sz : 1UL, hipHostMallocPortable );
-  if( e!=hipSuccess ) { tile_fail( "hipHostMalloc", e ); return NULL; }
-  return p;
-}
-
-void
-fd_ed25519_hip_host_free( void * ptr ) {
-  if( ptr ) hipHostFree( ptr );
-}
-
-/* the calling thread onto the CPUs of the device's NUMA node (within its
-   current affinity); no change when that cannot be read */
-static void
-pin_near_device( int device ) {
-  char bdf[ 64 ];
-  if( hipDeviceGetPCIBusId( bdf, (int)sizeof(bdf), device )!=hipSuccess ) return;
-  for( char * c=bdf; *c; c++ ) if( *c>='A' && *c<='F' ) *c = (char)(*c - 'A' + 'a');
-  char path[ 160 ];
-  snprintf( path, sizeof(path), "/sys/bus/pci/devices/%s/local_cpulist", bdf );
-  FILE * f = fopen( path, "r" );
-  if( !f ) return;
-  char list[ 1024 ];
-  size_t len = fread( list, 1, sizeof(list)-1UL, f );
-  fclose( f );
-  list[ len ] = 0;
-  cpu_set_t cur, want;
-  if( pthread_getaffinity_np( pthread_self(), sizeof(cur), &cur ) ) return;
-  CPU_ZERO( &want );
-  for( char * t=list; *t; ) {
-    char * e;
-    long lo = strtol( t, &e, 10 ), hi = lo;
-    if( e==t ) break;
-    if( *e=='-' ) { t = e+1; hi = strtol( t, &e, 10 ); }
-    for( long c=lo; c<=hi && c<CPU_SETSIZE; c++ ) if( c>=0 && CPU_ISSET( (int)c, &cur ) ) CPU_SET( (int)c, &want );
-    if( *e!=',' ) break;
-    t = e+1;
-  }
-  if( CPU_COUNT( &want ) ) pthread_setaffinity_np( pthread_self(), sizeof(want), &want );
-}
-
-/* a batch's message span [lo, hi) and its bytes */
-static void
-batch_span( pool_job_t const * j, unsigned long i0, unsigned long i1, unsigned long * lo, unsigned long * hi,
-            unsigned long * bytes ) {
-  unsigned long l = ~0UL, h = 0UL, b = 0UL;
-  for( unsigned long i=i0; i<i1; i++ ) {
-    unsigned long o = j->msg_off[i], e = o + j->msg_sz[i];
-    l = o<l ? o : l;
-    h = e>h ? e : h;
-    b += j->msg_sz[i];
-  }
-  if( l>h ) l = h = 0UL;
-  *lo = l; *hi = h; *bytes = b;
-}
-
-/* the span goes as it is when it fits and is not much larger than the
-   bytes in it */
-static int
-span_direct( fd_ed25519_hip_pool_t const * pl, unsigned long span, unsigned long bytes ) {
-  return span<=pl->msg_cap && span<=2UL*bytes + 65536UL;
-}
-
-static int
-pool_slot_init( pool_slot_t * s, int device, unsigned long batch_sigs, unsigned long msg_cap ) {
-  /* one stream per slot: the slots in flight overlap one another, a side
-     stream per slot would only crowd the device's hardware queues */
-  s->eng = fd_ed25519_hip_engine_new( device, batch_sigs, FD_ED25519_HIP_FLAG_ONE_STREAM );
-  if( !s->eng ) return FD_ED25519_HIP_ERR_INVAL;
-  unsigned long dsz = 112UL*batch_sigs + msg_cap + 64UL + 1024UL;
-  unsigned char * d = NULL;
-  TCHK( hipMalloc( (void **)&d, dsz ), "hipMalloc(pool slot)" );
-  s->d_sigs = d;                                     d += 64UL*batch_sigs;
-  s->d_pubs = d;                                     d += 32UL*batch_sigs;
-  s->d_off  = (unsigned long *)d;                    d += 8UL*batch_sigs;
-  s->d_sz   = (unsigned int *)d;                     d += 4UL*batch_sigs;
-  s->d_out  = (signed char *)d;                      d += (batch_sigs + 255UL) & ~255UL;
-  s->d_msgs = d;
-  TCHK( hipEventCreateWithFlags( &s->ev, hipEventDisableTiming ), "hipEventCreate" );
-  TCHK( hipEventCreateWithFlags( &s->ev_h2d, hipEventDisableTiming ), "hipEventCreate" );
-  return FD_ED25519_HIP_OK;
-}
-
-static void
-pool_slot_fini( pool_slot_t * s ) {
-  if( s->eng ) fd_ed25519_hip_engine_sync( s->eng );
-  hipFree( s->d_sigs );
-  hipHostFree( s->h_stage ); hipHostFree( s->h_out );
-  if( s->ev ) hipEventDestroy( s->ev );
-  if( s->ev_h2d ) hipEventDestroy( s->ev_h2d );
-  if( s->eng ) fd_ed25519_hip_engine_delete( s->eng );
-  memset( s, 0, sizeof(*s) );
-}
-
-void
-fd_ed25519_hip_pool_delete( fd_ed25519_hip_pool_t * pl ) {
-  if( !pl ) return;
-  for( unsigned r=0U; r<pl->device_cnt; r++ ) {
-    hipSetDevice( pl->device[r] );
-    for( unsigned k=0U; k<pl->slot_cnt; k++ ) pool_slot_fini( &pl->slot[r][k] );
-  }
-  free( pl );
-}
-
-fd_ed25519_hip_pool_t *
-fd_ed25519_hip_pool_new( int const * devices, unsigned device_cnt, unsigned slot_cnt, unsigned long batch_sigs,
-                         unsigned long msg_cap ) {
-  if( !devices || !device_cnt || device_cnt>POOL_DEV_MAX || slot_cnt<1U || slot_cnt>POOL_SLOT_MAX || !batch_sigs ) {
-    fd_ed25519_hip_private_set_error( "pool_new: 1..64 devices, 1..8 slots, batch_sigs > 0" );
-    return NULL;
-  }
-  fd_ed25519_hip_pool_t * pl = (fd_ed25519_hip_pool_t *)calloc( 1, sizeof(*pl) );
-  if( !pl ) return NULL;
-  pl->device_cnt = device_cnt; pl->slot_cnt = slot_cnt; pl->batch_sigs = batch_sigs;
-  pl->msg_cap = msg_cap ? msg_cap : 1UL;
-  for( unsigned r=0U; r<device_cnt; r++ ) {
-    pl->device[r] = devices[r];
-    if( hipSetDevice( devices[r] )!=hipSuccess ) { tile_fail( "hipSetDevice", hipErrorInvalidDevice ); goto fail; }
-    for( unsigned k=0U; k<slot_cnt; k++ )
-      if( pool_slot_init( &pl->slot[r][k], devices[r], batch_sigs, pl->msg_cap ) ) goto fail;
-  }
-  return pl;
-fail:
-  fd_ed25519_hip_pool_delete( pl );
-  return NULL;
-}
-
-static int
-pool_enqueue( pool_job_t * j, pool_slot_t * s, unsigned long b ) {
-  fd_ed25519_hip_pool_t * pl = j->pool;
-  unsigned long i0 = b*pl->batch_sigs, i1 = i0+pl->batch_sigs < j->n ? i0+pl->batch_sigs : j->n, cnt = i1-i0;
-  hipStream_t st = (hipStream_t)fd_ed25519_hip_engine_stream( s->eng );
-  unsigned long lo, hi, bytes;
-  batch_span( j, i0, i1, &lo, &hi, &bytes );
-  unsigned char const * dmsgs;
-  /* One batch crosses the link at a time: this batch's copies start once
-     the previous batch's are done (its kernels still overlap them).  Two
-     batches copying at once split the link between two DMA streams and
-     move fewer bytes in total than one (the host-fed rate fell to ~46M/s
-     with 3 slots, 69M/s with 2, depending on where the slots' streams
-     land on the device's hardware queues). */
-  if( j->h2d_tail ) TCHK( hipStreamWaitEvent( st, j->h2d_tail, 0U ), "hipStreamWaitEvent(h2d)" );
-  if( j->direct_in && span_direct( pl, hi-lo, bytes ) ) {
-    if( hi>lo ) TCHK( hipMemcpyAsync( s->d_msgs, j->msgs + lo, hi-lo, hipMemcpyHostToDevice, st ), "H2D msgs" );
-    TCHK( hipMemcpyAsync( s->d_off,  j->msg_off + i0, 8UL*cnt,  hipMemcpyHostToDevice, st ), "H2D off"  );
-    TCHK( hipMemcpyAsync( s->d_sz,   j->msg_sz  + i0, 4UL*cnt,  hipMemcpyHostToDevice, st ), "H2D sz"   );
-    TCHK( hipMemcpyAsync( s->d_sigs, j->sigs + 64UL*i0, 64UL*cnt, hipMemcpyHostToDevice, st ), "H2D sigs" );
-    TCHK( hipMemcpyAsync( s->d_pubs, j->pubs + 32UL*i0, 32UL*cnt, hipMemcpyHostToDevice, st ), "H2D pubs" );
-    j->st.direct_batches++;
-    j->st.h2d_bytes += (hi-lo) + 108UL*cnt;
-    dmsgs = s->d_msgs - lo;   /* msg_off[i] indexes the span from its start */
-  } else {
-    /* pack into pinned staging: [sigs | pubs | off | sz | msgs] */
-    if( bytes>pl->msg_cap ) {
-      fd_ed25519_hip_private_set_error( "pool: a batch's messages exceed the pool's msg_cap" );
-      return FD_ED25519_HIP_ERR_INVAL;
-    }
-    if( !s->h_stage )
-      TCHK( hipHostMalloc( (void **)&s->h_stage, 108UL*pl->batch_sigs + pl->msg_cap + 64UL, hipHostMallocDefault ),
-            "hipHostMalloc(pool stage)" );
-    unsigned char * h = s->h_stage;
-    memcpy( h,               j->sigs + 64UL*i0, 64UL*cnt );
-    memcpy( h + 64UL*cnt,    j->pubs + 32UL*i0, 32UL*cnt );
-    unsigned long * off = (unsigned long *)(h + 96UL*cnt);
-    unsigned int *  sz  = (unsigned int  *)(h + 104UL*cnt);
-    unsigned char * m   = h + 108UL*cnt;
-    unsigned long pos = 0UL;
-    for( unsigned long i=i0; i<i1; i++ ) {
-      unsigned long k = i-i0;
-      if( j->msg_sz[i] ) memcpy( m + pos, j->msgs + j->msg_off[i], j->msg_sz[i] );
-      off[k] = pos; sz[k] = j->msg_sz[i];
-      pos += j->msg_sz[i];
-    }
-    TCHK( hipMemcpyAsync( s->d_sigs, h,            64UL*cnt, hipMemcpyHostToDevice, st ), "H2D sigs" );
-    TCHK( hipMemcpyAsync( s->d_pubs, h + 64UL*cnt, 32UL*cnt, hipMemcpyHostToDevice, st ), "H2D pubs" );
-    TCHK( hipMemcpyAsync( s->d_off,  off,          8UL*cnt,  hipMemcpyHostToDevice, st ), "H2D off"  );
-    TCHK( hipMemcpyAsync( s->d_sz,   sz,           4UL*cnt,  hipMemcpyHostToDevice, st ), "H2D sz"   );
-    if( pos ) TCHK( hipMemcpyAsync( s->d_msgs, m, pos, hipMemcpyHostToDevice, st ), "H2D msgs" );
-    j->st.staged_batches++;
-    j->st.h2d_bytes += pos + 108UL*cnt;
-    dmsgs = s->d_msgs;
-  }
-  TCHK( hipEventRecord( s->ev_h2d, st ), "hipEventRecord(h2d)" );
-  j->h2d_tail = s->ev_h2d;
-#ifdef FD_ED25519_HIP_HOST_FAULT
-  /* test build only (tests/test_gpu_pool_fault.py): the second batch's
-     launch fails after its copies from the caller's arrays are enqueued */
-  if( b==1UL ) {
-    fd_ed25519_hip_private_set_error( "pool: injected launch failure (fault-injection build)" );
-    return FD_ED25519_HIP_ERR_HIP - (int)hipErrorLaunchFailure;
-  }
-#endif
-  int err = fd_ed25519_hip_verify_dev( s->eng, cnt, dmsgs, s->d_off, s->d_sz, s->d_sigs, s->d_pubs, s->d_out, st );
-  if( err ) return err;
-  if( !j->direct_out && !s->h_out )
-    TCHK( hipHostMalloc( (void **)&s->h_out, pl->batch_sigs, hipHostMallocDefault ), "hipHostMalloc(pool out)" );
-  signed char * dst = j->direct_out ? j->out + i0 : s->h_out;
-  TCHK( hipMemcpyAsync( dst, s->d_out, cnt, hipMemcpyDeviceToHost, st ), "D2H codes" );
-  TCHK( hipEventRecord( s->ev, st ), "hipEventRecord" );
-  s->i0 = i0; s->i1 = i1; s->busy = 1;
-  return FD_ED25519_HIP_OK;
-}
-
-/* A batch whose enqueue failed part way may have left copies from or into
-   the caller's page-locked arrays on the slot's stream: they finish before
-   the error is reported, so pool_run never returns while DMA may still
-   touch memory the caller is free to release. */
-static int
-pool_submit( pool_job_t * j, pool_slot_t * s, unsigned long b ) {
-  int err = pool_enqueue( j, s, b );
-  if( err ) hipStreamSynchronize( (hipStream_t)fd_ed25519_hip_engine_stream( s->eng ) );
-  return err;
-}
-
-static void *
-pool_main( void * arg ) {
-  pool_job_t * j = (pool_job_t *)arg;
-  fd_ed25519_hip_pool_t * pl = j->pool;
-  int dev = pl->device[ j->rank ];
-  pin_near_device( dev );
-  if( hipSetDevice( dev )!=hipSuccess ) {
-    j->err = tile_fail( "hipSetDevice", hipErrorInvalidDevice );
-    snprintf( j->errmsg, sizeof(j->errmsg), "%s", fd_ed25519_hip_last_error() );
-    return NULL;
-  }
-  pool_slot_t * slot = pl->slot[ j->rank ];
-  unsigned sc = pl->slot_cnt, ranks = pl->device_cnt;
-  unsigned long nb = (j->n + pl->batch_sigs - 1UL) / pl->batch_sigs;
-  unsigned long b_sub = j->rank, b_done = j->rank;
-  unsigned next = 0U, oldest = 0U;
-  while( b_done<nb ) {
-    pool_slot_t * s = &slot[ next ];
-    if( !j->err && b_sub<nb && !s->busy ) {
-      int err = pool_submit( j, s, b_sub );
-      if( err ) {   /* drain what is in flight */
-        j->err = err;
-        snprintf( j->errmsg, sizeof(j->errmsg), "%s", fd_ed25519_hip_last_error() );
-        continue;
-      }
-      b_sub += ranks;
-      next = (next+1U) % sc;
-      continue;
-    }
-    pool_slot_t * d = &slot[ oldest ];
-    if( !d->busy ) break;   /* an error stopped submission and everything drained */
-    hipError_t e = hipEventSynchronize( d->ev );
-    if( e!=hipSuccess && !j->err ) {
-      j->err = tile_fail( "pool batch", e );
-      snprintf( j->errmsg, sizeof(j->errmsg), "%s", fd_ed25519_hip_last_error() );
-    }
-    if( !j->direct_out && e==hipSuccess ) memcpy( j->out + d->i0, d->h_out, d->i1 - d->i0 );
-    d->busy = 0;
-    oldest = (oldest+1U) % sc;
-    b_done += ranks;
-  }
-  return NULL;
-}
-
-int
-fd_ed25519_hip_pool_run( fd_ed25519_hip_pool_t * pl, unsigned long n, unsigned char const * msgs,
-                         unsigned long const * msg_off, unsigned int const * msg_sz, unsigned char const * sigs,
-                         unsigned char const * pubs, signed char * out, double * seconds,
-                         fd_ed25519_hip_pool_stats_t * stats ) {
-  if( !pl || !out ) return FD_ED25519_HIP_ERR_INVAL;
-  if( n && (!msg_off || !msg_sz || !sigs || !pubs || !msgs) ) return FD_ED25519_HIP_ERR_INVAL;
-  pool_job_t job[ POOL_DEV_MAX ];
-  pthread_t  th[ POOL_DEV_MAX ];
-  int direct_in  = n && host_locked( msgs ) && host_locked( msg_off ) && host_locked( msg_sz ) &&
-                   host_locked( sigs ) && host_locked( pubs );
-  int direct_out = n && host_locked( out );
-  double t0 = now_s();
-  unsigned started = 0U;
-  int err = 0;
-  for( unsigned r=0U; r<pl->device_cnt; r++ ) {
-    memset( &job[r], 0, sizeof(job[r]) );
-    job[r].pool = pl; job[r].rank = r; job[r].n = n; job[r].msgs = msgs; job[r].msg_off = msg_off;
-    job[r].msg_sz = msg_sz; job[r].sigs = sigs; job[r].pubs = pubs; job[r].out = out;
-    job[r].direct_in = direct_in; job[r].direct_out = direct_out;
-    if( pthread_create( &th[r], NULL, pool_main, &job[r] ) ) { err = FD_ED25519_HIP_ERR_NOMEM; break; }
-    started++;
-  }
-  if( stats ) memset( stats, 0, sizeof(*stats) );
-  for( unsigned r=0U; r<started; r++ ) {
-    pthread_join( th[r], NULL );
-    if( job[r].err && !err ) { err = job[r].err; fd_ed25519_hip_private_set_error( job[r].errmsg ); }
-    if( stats ) {
-      stats->direct_batches += job[r].st.direct_batches;
-      stats->staged_batches += job[r].st.staged_batches;
-      stats->h2d_bytes      += job[r].st.h2d_bytes;
-    }
-  }
-  if( seconds ) *seconds = now_s() - t0;
-  return err;
-}
-
-int
-fd_ed25519_hip_pool_verify( int const * devices, unsigned device_cnt, unsigned slot_cnt, unsigned long batch_sigs,
-                            unsigned long n, unsigned char const * msgs, unsigned long const * msg_off,
-                            unsigned int const * msg_sz, unsigned char const * sigs, unsigned char const * pubs,
-                            signed char * out, double * seconds ) {
-  if( !batch_sigs ) return FD_ED25519_HIP_ERR_INVAL;
-  /* capacity: the largest span of a batch */
-  unsigned long cap = 1UL;
-  pool_job_t tmp;
-  memset( &tmp, 0, sizeof(tmp) );
-  tmp.msg_off = msg_off; tmp.msg_sz = msg_sz;
-  for( unsigned long i0=0UL; n && msg_off && msg_sz && i0<n; i0+=batch_sigs ) {
-    unsigned long lo, hi, bytes;
-    batch_span( &tmp, i0, i0+batch_sigs<n ? i0+batch_sigs : n, &lo, &hi, &bytes );
-    unsigned long need = hi-lo<=2UL*bytes + 65536UL ? hi-lo : bytes;
-    if( need>cap ) cap = need;
-  }
-  fd_ed25519_hip_pool_t * pl = fd_ed25519_hip_pool_new( devices, device_cnt, slot_cnt, batch_sigs, cap );
-  if( !pl ) return FD_ED25519_HIP_ERR_INVAL;
-  double t0 = now_s();
-  int err = fd_ed25519_hip_pool_run( pl, n, msgs, msg_off, msg_sz, sigs, pubs, out, NULL, NULL );
-  fd_ed25519_hip_pool_delete( pl );
-  if( seconds ) *seconds = now_s() - t0;
-  return err;
-}
-
-double
-fd_ed25519_hip_h2d_gbps( int device, unsigned long bytes, unsigned reps ) {
-  if( !bytes || !reps || hipSetDevice( device )!=hipSuccess ) return 0.0;
-  void * h = NULL, * d = NULL;
-  hipStream_t st = NULL;
-  double r = 0.0;
-  if( hipHostMalloc( &h, bytes, hipHostMallocDefault )==hipSuccess && hipMalloc( &d, bytes )==hipSuccess &&
-      hipStreamCreateWithFlags( &st, hipStreamNonBlocking )==hipSuccess ) {
-    memset( h, 0x5a, bytes );
-    int ok = hipMemcpyAsync( d, h, bytes, hipMemcpyHostToDevice, st )==hipSuccess &&
-             hipStreamSynchronize( st )==hipSuccess;   /* warm-up */
-    double t0 = now_s();
-    for( unsigned i=0U; ok && i<reps; i++ ) ok = hipMemcpyAsync( d, h, bytes, hipMemcpyHostToDevice, st )==hipSuccess;
-    ok = ok && hipStreamSynchronize( st )==hipSuccess;
-    double dt = now_s() - t0;
-    if( ok && dt>0.0 ) r = (double)bytes * reps / dt * 1e-9;
-  }
-  if( st ) hipStreamDestroy( st );
-  hipFree( d ); hipHostFree( h );
-  return r;
 }

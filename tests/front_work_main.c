@@ -2,7 +2,7 @@
    against the public FD_ED25519_HIP_*_WORK_BYTES macros a caller sizes the
    buffer with, and against the byte offsets the engine used before the
    layouts had a header of their own (written out below as they stood in
-   fd_ed25519_hip_engine.c).  Stand-alone, built under ASan and UBSan by
+   fd_ed25519_hip_engine.c, the fronts' file then).  Stand-alone, built under ASan and UBSan by
    tests/test_front_work.py; only pointers are formed, no array is touched.
 
    Prints the number of layouts checked; exit 1 with the first failure. */
