@@ -654,6 +654,24 @@ int fd_ed25519_hip_launch_fec_scatter( fd_ed25519_fec_scatter_params_t const * p
 /* the tree kernel's workgroup size as built (tools/fec_bench.py reports it) */
 unsigned fd_ed25519_hip_private_fec_tree_block( void );
 
+/* ---- the Reed-Solomon parity of a leader's FEC sets (fd_ed25519_reedsol.hip) ---- */
+
+/* parity: workgroup k applies fd_fec_core.h's and fd_reedsol_core.h's rules
+   to the shreds [set_first[k], set_first[k+1]) and, when they pass, writes
+   bytes [0x59, 0x59 + P) of the set's code shreds and nothing else */
+typedef struct {
+  uint8_t *        shreds;     /* shred bytes, readable 16 B past each      */
+  uint64_t const * shred_off;  /* [n]                                       */
+  uint32_t const * shred_sz;   /* [n]                                       */
+  uint64_t         n;
+  uint32_t const * set_first;  /* [n_set+1]                                 */
+  uint64_t         n_set;
+  uint8_t const *  tab;        /* fd_reedsol_core_tables's block, 16-B aligned */
+  int8_t *         set_out;    /* [n_set] out: 0, ERR_PARSE, UNSUPPORTED, ERR_SET */
+} fd_ed25519_fec_parity_params_t;
+
+int fd_ed25519_hip_launch_fec_parity( fd_ed25519_fec_parity_params_t const * p, void * stream );
+
 /* ---- generator (fd_ed25519_gen.hip) ---- */
 
 typedef struct {

@@ -30,6 +30,7 @@ struct fd_ed25519_hip_engine {
   int32_t *    d_btab16;     /* [0..2^15]B, the verify kernels' wide B table  */
   int32_t *    btabw[2];    /* shared per device: [0..2^24)B, [0..2^24)[2^144]B */
   int32_t *    btabs[2][8]; /* shared per device: dsm16s<4>'s and <8>'s compact tables, when acquired */
+  uint8_t *    d_rstab;     /* the parity kernel's product and coefficient tables (fd_reedsol_core.h) */
   /* Pipeline lanes: the per-chunk scratch of a chunk in flight, and the
      streams its phases run on.  Lane 0 runs on the caller's stream (or the
      engine's); the chunks of a multi-chunk call alternate between lane 0
@@ -97,5 +98,9 @@ int fd_ed25519_hip_private_verify_common( fd_ed25519_hip_engine_t * e, unsigned 
    message staging (h_msgs, d_msgs) grown to bytes */
 int fd_ed25519_hip_private_grow_pair( void ** h, void ** d, uint64_t * cap, uint64_t need, uint64_t elem );
 int fd_ed25519_hip_private_stage_msgs( fd_ed25519_hip_engine_t * e, uint64_t bytes );
+/* the parity kernel's tables (fd_reedsol_core_tables, in the fronts' file with the other cores): their size, and
+   the bytes into tab */
+unsigned long fd_ed25519_hip_private_reedsol_tab_bytes( void );
+void fd_ed25519_hip_private_reedsol_tables( unsigned char * tab );
 
 #endif

@@ -1,8 +1,8 @@
 /* fd_ed25519_hip_fronts.c -- the fronts before the verify phases
-   (include/fd_ed25519_hip.h Parts 2b-2f): stage kernel, verify_common,
+   (include/fd_ed25519_hip.h Parts 2b-2g): stage kernel, verify_common,
    finish kernel in a *_dev; pack, upload, *_dev, download, synchronise in a
    *_host ("The shape of a front"); and the rules the stage
-   kernels run, on the host (*_count, *_plan, *_root).  Part of the engine:
+   kernels run, on the host (*_count, *_plan, *_root, fec_parity).  Part of the engine:
    the *_host wrappers stage in its pinned buffers
    (fd_ed25519_hip_engine_fields.h). */
 
@@ -15,6 +15,7 @@
 #include "../fd_packet_core.h"
 #include "../fd_crds_core.h"
 #include "../fd_fec_core.h"
+#include "../fd_reedsol_core.h"
 #include "../fd_front_work.h"
 
 #include <string.h>
@@ -627,6 +628,134 @@ fd_ed25519_hip_fec_seal_host( fd_ed25519_hip_engine_t * e, unsigned long n, unsi
         uint64_t proof_at = ( ( src[ 0x40 ] & 0xf0 )==0x80 ? FD_SHRED_CORE_MIN_SZ : FD_SHRED_CORE_MAX_SZ ) - 20UL*depth;
         if( privs ) memcpy( dst, src, 64UL );
         memcpy( dst + proof_at, src + proof_at, 20UL*depth );
+      }
+    }
+    k0 = k1;
+  }
+  return FD_ED25519_HIP_OK;
+}
+
+/* ---- the Reed-Solomon parity of a leader's FEC sets (include/fd_ed25519_hip.h Part 2g) -- */
+
+unsigned long
+fd_ed25519_hip_private_reedsol_tab_bytes( void ) { return FD_REEDSOL_CORE_TAB_BYTES; }
+
+void
+fd_ed25519_hip_private_reedsol_tables( unsigned char * tab ) { fd_reedsol_core_tables( tab ); }
+
+/* the rules and the code the parity kernel runs, on the host (no GPU) */
+int
+fd_ed25519_hip_fec_parity( unsigned char * shreds, unsigned long const * shred_off, unsigned int const * shred_sz,
+                           unsigned long cnt ) {
+  return fd_reedsol_core_encode( shreds, shred_off, shred_sz, cnt );
+}
+
+int
+fd_ed25519_hip_fec_parity_dev( fd_ed25519_hip_engine_t * e, unsigned long n, unsigned char * shreds,
+                               unsigned long const * shred_off, unsigned int const * shred_sz, unsigned long n_set,
+                               unsigned int const * set_first, signed char * set_out, void * stream ) {
+  hipStream_t st;
+  int err = front_begin( e, n_set, set_first && set_out && ( !n || ( shreds && shred_off && shred_sz ) ) &&
+                                   n<=UINT32_MAX && n_set<=INT32_MAX, (uintptr_t)shreds, "shreds", stream, &st );
+  if( err<=0 ) return err;
+  fd_ed25519_fec_parity_params_t pp = { 0 };
+  pp.shreds = shreds; pp.shred_off = (uint64_t const *)shred_off; pp.shred_sz = shred_sz; pp.n = n;
+  pp.set_first = set_first; pp.n_set = n_set; pp.tab = e->d_rstab; pp.set_out = (int8_t *)set_out;
+  HIPCHK( (hipError_t)fd_ed25519_hip_launch_fec_parity( &pp, st ), "fec_parity launch" );
+  return FD_ED25519_HIP_OK;
+}
+
+/* a shred that travels as its header: a code shred (type 0x4?) keeps its
+   1228 bytes on the device, where the kernel fills them, and sends its first
+   0x59 -- no rule reads a byte at or past 0x59 */
+static int
+parity_travels_as_header( unsigned char const * s, uint64_t sz ) {
+  return sz>0x40UL && ( s[ 0x40 ] & 0xf0 )==0x40;
+}
+
+/* Pass by pass, whole sets at a time, as fec_seal_host.  A pass's staging,
+   the same on the host and on the device: the shreds that travel whole back
+   to back (the data shreds; capped at FD_SHRED_MAX_SZ as the seal's), then,
+   from the next 16-byte boundary, the code shreds 1228 bytes apart.  Up go
+   the first part as it is and bytes [0, 0x59) of every code shred (one
+   strided copy); down comes the second part.
+   in: off u64 [m], set_first u32 [ms+1], sz u32 [m]; out: codes [ms].  Of a
+   set with code 0 the parity regions of its code shreds are copied back,
+   nothing else. */
+int
+fd_ed25519_hip_fec_parity_host( fd_ed25519_hip_engine_t * e, unsigned long n, unsigned char * shreds,
+                                unsigned long const * shred_off, unsigned int const * shred_sz, unsigned long n_set,
+                                unsigned int const * set_first, signed char * set_out ) {
+  hipStream_t st;
+  int err = front_begin( e, n_set, set_first && set_out && ( !n || ( shreds && shred_off && shred_sz ) ) && n<=UINT32_MAX,
+                         0UL, NULL, NULL, &st );
+  if( err<=0 ) return err;
+  for( uint64_t k0=0UL; k0<n_set; ) {
+    uint64_t k1 = k0, m = 0UL;
+    for( ; k1<n_set && k1-k0<FRONT_HOST_CHUNK; k1++ ) {
+      uint64_t first = set_first[k1], last = set_first[k1+1UL];
+      uint64_t cnt = ( first<=last && last<=n && last-first<=FD_FEC_CORE_CNT_MAX ) ? last-first : 0UL;
+      if( m+cnt>FRONT_HOST_CHUNK ) break;
+      m += cnt;
+    }
+    uint64_t ms = k1-k0;
+    uint64_t first_at = 8UL*m, sz_at = first_at + 4UL*( ms+1UL ), in_bytes = sz_at + 4UL*m;
+    if( (err = front_room( e, m*FD_SHRED_CORE_MAX_SZ + 16UL, in_bytes, ms )) ) return err;
+    uint64_t * h_off   = (uint64_t *)e->h_fr_in;
+    uint32_t * h_first = (uint32_t *)( e->h_fr_in + first_at );
+    uint32_t * h_sz    = (uint32_t *)( e->h_fr_in + sz_at );
+    /* the whole shreds first: where they end, the code shreds begin */
+    uint64_t whole = 0UL, i = 0UL;
+    for( uint64_t k=k0; k<k1; k++ ) {
+      uint64_t first = set_first[k], last = set_first[k+1UL];
+      uint64_t cnt = ( first<=last && last<=n && last-first<=FD_FEC_CORE_CNT_MAX ) ? last-first : 0UL;
+      for( uint64_t j=first; j<first+cnt; j++ )
+        if( !parity_travels_as_header( shreds + shred_off[j], shred_sz[j] ) )
+          whole += shred_sz[j]<=FD_SHRED_CORE_MAX_SZ ? shred_sz[j] : FD_SHRED_CORE_MAX_SZ;
+    }
+    uint64_t code_at = ( whole+15UL ) & ~15UL, pos = 0UL, n_code = 0UL;
+    for( uint64_t k=k0; k<k1; k++ ) {
+      uint64_t first = set_first[k], last = set_first[k+1UL];
+      uint64_t cnt = ( first<=last && last<=n && last-first<=FD_FEC_CORE_CNT_MAX ) ? last-first : 0UL;
+      h_first[ k-k0 ] = (uint32_t)i;
+      for( uint64_t j=first; j<first+cnt; j++, i++ ) {
+        unsigned char const * s = shreds + shred_off[j];
+        h_sz[i] = shred_sz[j];
+        if( parity_travels_as_header( s, shred_sz[j] ) ) {
+          uint64_t cp = shred_sz[j]<FD_SHRED_CORE_CODE_HDR_SZ ? shred_sz[j] : FD_SHRED_CORE_CODE_HDR_SZ;
+          h_off[i] = code_at + FD_SHRED_CORE_MAX_SZ*n_code++;
+          memset( e->h_msgs + h_off[i], 0, FD_SHRED_CORE_CODE_HDR_SZ );
+          memcpy( e->h_msgs + h_off[i], s, cp );
+        } else {
+          uint64_t cp = shred_sz[j]<=FD_SHRED_CORE_MAX_SZ ? shred_sz[j] : FD_SHRED_CORE_MAX_SZ;
+          if( cp ) memcpy( e->h_msgs + pos, s, cp );
+          h_off[i] = pos;
+          pos += cp;
+        }
+      }
+    }
+    h_first[ ms ] = (uint32_t)i;
+    if( (err = front_upload( e, pos, in_bytes, st )) ) return err;
+    if( n_code )
+      HIPCHK( hipMemcpy2DAsync( e->d_msgs + code_at, FD_SHRED_CORE_MAX_SZ, e->h_msgs + code_at, FD_SHRED_CORE_MAX_SZ,
+                                FD_SHRED_CORE_CODE_HDR_SZ, n_code, hipMemcpyHostToDevice, st ), "H2D parity headers" );
+    err = fd_ed25519_hip_fec_parity_dev( e, m, e->d_msgs, (unsigned long const *)e->d_fr_in,
+                                         (unsigned int const *)( e->d_fr_in + sz_at ), ms,
+                                         (unsigned int const *)( e->d_fr_in + first_at ), (signed char *)e->d_fr_out, st );
+    if( err ) return err;
+    if( n_code )
+      HIPCHK( hipMemcpyAsync( e->h_msgs + code_at, e->d_msgs + code_at, FD_SHRED_CORE_MAX_SZ*n_code, hipMemcpyDeviceToHost, st ),
+              "D2H parity shreds" );
+    if( (err = front_download( e, ms, st )) ) return err;
+    memcpy( set_out + k0, e->h_fr_out, ms );
+    for( uint64_t k=k0; k<k1; k++ ) {
+      if( set_out[k] ) continue;                      /* rule 8 */
+      uint64_t first = set_first[k], cnt = set_first[k+1UL]-first;
+      uint64_t region = FD_REEDSOL_CORE_REGION( fd_fec_core_depth( (unsigned)cnt ) );
+      for( uint64_t j=0UL; j<cnt; j++ ) {
+        uint64_t at = h_off[ h_first[ k-k0 ]+j ];
+        if( at<code_at ) continue;                    /* a data shred: read only */
+        memcpy( shreds + shred_off[ first+j ] + FD_SHRED_CORE_CODE_HDR_SZ, e->h_msgs + at + FD_SHRED_CORE_CODE_HDR_SZ, region );
       }
     }
     k0 = k1;

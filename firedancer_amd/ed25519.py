@@ -204,6 +204,32 @@ def fec_root(shreds):
     return code, root.raw, [proofs[width * j:width * (j + 1)].tobytes() for j in range(cnt)]
 
 
+# the Reed-Solomon parity of a leader's FEC sets (include/fd_ed25519_hip.h Part 2g)
+_lib.fd_ed25519_hip_fec_parity.argtypes = [_u8p, _u8p, _u8p, ctypes.c_ulong]
+_lib.fd_ed25519_hip_fec_parity_dev.argtypes = [ctypes.c_void_p, ctypes.c_ulong] + [_u8p] * 3 + [ctypes.c_ulong] + [_u8p] * 3
+_lib.fd_ed25519_hip_fec_parity_host.argtypes = [ctypes.c_void_p, ctypes.c_ulong] + [_u8p] * 3 + [ctypes.c_ulong] + [_u8p] * 2
+
+
+def fec_parity_region(cnt):
+    """bytes of a shred the code protects in a set of cnt shreds: [0x40, +P)
+    of a data shred, [0x59, +P) of a code shred"""
+    return 1139 - 20 * fec_depth(cnt)
+
+
+def fec_parity(shreds):
+    """fd_ed25519_hip_fec_parity: (code, the shreds after the call) of one
+    FEC set given as its raw shreds in tree order -- the parity regions of
+    its code shreds filled when the code is 0, nothing changed otherwise
+    (host only)."""
+    from .tile import pack_payloads
+    cnt = len(shreds)
+    if not cnt:
+        return _lib.fd_ed25519_hip_fec_parity(None, None, None, 0), []
+    buf, off, sz = pack_payloads([bytes(s) for s in shreds])
+    code = _lib.fd_ed25519_hip_fec_parity(_ptr(buf), _ptr(off), _ptr(sz), cnt)
+    return code, [buf[int(off[i]):int(off[i]) + int(sz[i])].tobytes() for i in range(cnt)]
+
+
 # signed gossip and repair control packets (include/fd_ed25519_hip.h Part 2d)
 PROTO_GOSSIP = 0
 PROTO_REPAIR_SERV = 1
@@ -559,6 +585,35 @@ class Engine:
         """Device-resident fd_ed25519_hip_fec_seal_dev: device addresses (ints); async."""
         _check(_lib.fd_ed25519_hip_fec_seal_dev(self._h, int(n), d_shreds, d_off, d_sz, int(n_set), d_set_first, d_privs,
                                                 d_work, d_set_out, d_roots, d_sigs, stream))
+
+    def fec_parity_flat(self, shreds, set_first):
+        """fd_ed25519_hip_fec_parity_host on shreds (a list of raw shreds)
+        whose set k is shreds[set_first[k]:set_first[k + 1]] in tree order ->
+        (int8 code per set, the shreds after the call); synchronous."""
+        from .tile import pack_payloads
+        n, n_set = len(shreds), len(set_first) - 1
+        first = _c(set_first, np.uint32)
+        codes = np.zeros(max(1, n_set), np.int8)
+        buf, off, sz = pack_payloads([bytes(s) for s in shreds]) if n else (np.zeros(1, np.uint8),) * 3
+        _check(_lib.fd_ed25519_hip_fec_parity_host(self._h, n, _ptr(buf), _ptr(off), _ptr(sz), n_set, _ptr(first), _ptr(codes)))
+        return codes[:n_set], [buf[int(off[i]):int(off[i]) + int(sz[i])].tobytes() for i in range(n)]
+
+    def fec_parity_host(self, sets):
+        """Fills the parity shreds of FEC sets (fd_ed25519_hip_fec_parity_host):
+        sets is a list of sets, each the list of its raw shreds in tree order
+        (data, then parity, of which the first 0x59 bytes are read) -> (int8
+        code per set, the sets with the parity regions written where the code
+        is 0); synchronous."""
+        first = [0]
+        for s in sets:
+            first.append(first[-1] + len(s))
+        codes, flat = self.fec_parity_flat([x for s in sets for x in s], first)
+        return codes, [flat[first[k]:first[k + 1]] for k in range(len(sets))]
+
+    def fec_parity_dev(self, n, d_shreds, d_off, d_sz, n_set, d_set_first, d_set_out, stream=None):
+        """Device-resident fd_ed25519_hip_fec_parity_dev: device addresses (ints); async."""
+        _check(_lib.fd_ed25519_hip_fec_parity_dev(self._h, int(n), d_shreds, d_off, d_sz, int(n_set), d_set_first, d_set_out,
+                                                  stream))
 
     # ---- batched signing / synthetic workloads -------------------------
     def sign_dev(self, n, d_msgs, d_off, d_sz, d_privs, d_sigs, d_pubs, stream=None):

@@ -213,14 +213,15 @@ typedef struct fd_ed25519_hip_engine fd_ed25519_hip_engine_t;
    instructions of raw transactions; 12: Part 2c, the leader signatures of
    Merkle shreds; 13: Part 2d, signed gossip and repair control packets; 14:
    Part 2e, the CRDS values of gossip pull responses and push messages; 15:
-   Part 2f, sealing a leader's FEC sets).
+   Part 2f, sealing a leader's FEC sets; 16: Part 2g, the Reed-Solomon
+   parity of a leader's FEC sets).
    A consumer checks
    the library it loaded against the header it was built with:
    fd_ed25519_hip_abi_check( FD_ED25519_HIP_ABI_VERSION,
    sizeof(fd_ed25519_hip_slot_t), sizeof(fd_ed25519_hip_info_t),
    sizeof(fd_ed25519_hip_vservice_stats_t) ) returns 0 when they agree,
    FD_ED25519_HIP_ERR_INVAL (with fd_ed25519_hip_last_error) when not. */
-#define FD_ED25519_HIP_ABI_VERSION (15U)
+#define FD_ED25519_HIP_ABI_VERSION (16U)
 
 unsigned
 fd_ed25519_hip_abi_version( void );
@@ -1003,10 +1004,10 @@ fd_ed25519_hip_crds_host( fd_ed25519_hip_engine_t * engine,
    key's public key.  All four codes are this library's; they reuse Part
    2c's numbering.
 
-   Out of scope: the Reed-Solomon parity itself (the caller hands in filled
-   parity shreds, as fd_shredder.c:167-223 produces them before the tree),
-   the construction of shred headers, and chained and resigned variants,
-   which the reference's shredder does not emit. */
+   The parity shreds come in filled, as fd_shredder.c:167-223 produces them
+   before the tree: Part 2g fills them on the device.  Out of scope: the
+   construction of shred headers, and chained and resigned variants, which
+   the reference's shredder does not emit. */
 #define FD_ED25519_HIP_FEC_OK          (  0)
 #define FD_ED25519_HIP_FEC_ERR_PARSE   (-16)
 #define FD_ED25519_HIP_FEC_UNSUPPORTED (-18)
@@ -1098,6 +1099,83 @@ fd_ed25519_hip_fec_seal_host( fd_ed25519_hip_engine_t * engine,
                               signed char *             set_out,
                               unsigned char *           roots,
                               unsigned char *           sigs );
+
+/* ---- Part 2g: the Reed-Solomon parity of a leader's FEC sets ------------ */
+
+/* The step before the seal.  fd_shredder_next_fec_set fills a set's parity
+   shreds from its data shreds (fd_reedsol_encode_fini,
+   src/disco/shred/fd_shredder.c:167-223) and only then builds the tree.  The
+   entry points below take sets whose data shreds and parity headers (the
+   first 0x59 bytes of a code shred) are filled and compute the parity.
+   Followed by Part 2f over the same arrays they are fd_shredder_next_fec_set
+   from line 167 on.
+
+   The code is the reference's: over GF(2^8) with the polynomial 0x11D, byte
+   b of parity shred j of a set of d data shreds is P_b( d + j ), P_b the
+   polynomial of degree < d with P_b( i ) = byte b of data shred i.  The
+   bytes it protects, with P = 1139 - 20 depth and depth the proof depth of
+   the set's d + p shreds: [0x40, 0x40 + P) of a data shred, [0x59,
+   0x59 + P) of a code shred -- both end where the proof begins.
+
+   A set is judged as in Part 2f, with the same four codes, and then shred
+   by shred, the first failing shred deciding as there: a data shred behind
+   a code shred, a 68th data shred, a data shred as the set's last (no
+   parity), a code shred at place 0 (no data), and a code shred whose
+   data_cnt is not the set's number of data shreds or whose code_cnt is not
+   its number of code shreds get FEC_ERR_SET (Part 2f takes a code shred's
+   counts as they come; the parity cannot).  In a set with code 0 exactly
+   the bytes [0x59, 0x59 + P) of every code shred are written; a set with a
+   code has no byte of any of its shreds written. */
+
+/* One set, host only (no GPU), from the same source as the device's kernel.
+   Shred j of the set is shreds[shred_off[j] .. shred_off[j] + shred_sz[j]),
+   j < cnt; shreds do not overlap.  Returns 0 with the parity regions of the
+   set's code shreds written in place, else the set's code with nothing
+   written. */
+int
+fd_ed25519_hip_fec_parity( unsigned char *       shreds,
+                           unsigned long const * shred_off,
+                           unsigned int const *  shred_sz,
+                           unsigned long         cnt );
+
+/* Device-resident batch: every pointer but the engine is a device pointer,
+   with fd_ed25519_hip_fec_seal_dev's rules for them: shred i is
+   shreds[shred_off[i] .. shred_off[i] + shred_sz[i]) and may start at any
+   byte; shreds do not overlap; the buffer starts 16-byte aligned and stays
+   readable at least 16 bytes past the end of the last shred; set k is the
+   shreds [set_first[k], set_first[k+1]) in tree order, and a range that
+   runs backwards or leaves [0, n) gets FEC_ERR_SET and touches nothing.
+   n < 2^32, n_set < 2^31.  set_out[k] receives the set's code.
+
+   Asynchronous on `stream` (NULL: the engine's): one launch, whose tables
+   the engine made when it was created; no workspace, no allocation, no
+   synchronisation.  n_set==0 is a no-op. */
+int
+fd_ed25519_hip_fec_parity_dev( fd_ed25519_hip_engine_t * engine,
+                               unsigned long             n,
+                               unsigned char *           shreds,
+                               unsigned long const *     shred_off,
+                               unsigned int const *      shred_sz,
+                               unsigned long             n_set,
+                               unsigned int const *      set_first,
+                               signed char *             set_out,
+                               void *                    stream );
+
+/* Host-buffer batch, synchronous: packs whole sets into pinned staging
+   memory (in passes, so any n fits) -- a code shred travels as its first
+   0x59 bytes and its size, since the device writes the rest --, copies, runs
+   fec_parity_dev and copies back set_out[0..n_set) and, into the caller's
+   code shreds of every set with code 0, the parity region -- nothing else.
+   No alignment is asked of any argument. */
+int
+fd_ed25519_hip_fec_parity_host( fd_ed25519_hip_engine_t * engine,
+                                unsigned long             n,
+                                unsigned char *           shreds,
+                                unsigned long const *     shred_off,
+                                unsigned int const *      shred_sz,
+                                unsigned long             n_set,
+                                unsigned int const *      set_first,
+                                signed char *             set_out );
 
 /* ---- Part 3: batched signing and the synthetic workload generator ------ */
 
