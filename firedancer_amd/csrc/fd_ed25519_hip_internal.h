@@ -672,6 +672,25 @@ typedef struct {
 
 int fd_ed25519_hip_launch_fec_parity( fd_ed25519_fec_parity_params_t const * p, void * stream );
 
+/* ---- recovering received FEC sets (fd_ed25519_recover.hip) ---- */
+
+/* recover: workgroup k applies fd_fec_core.h's and fd_reedsol_core.h's rules
+   9-11 to the slots [set_first[k], set_first[k+1]) and, when they pass,
+   writes what rule 12 names of the set's erased slots and nothing else */
+typedef struct {
+  uint8_t *        shreds;     /* slot bytes, readable 16 B past each       */
+  uint64_t const * shred_off;  /* [n]                                       */
+  uint32_t const * shred_sz;   /* [n]                                       */
+  uint8_t const *  erased;     /* [n] 0: received, else erased (not read)   */
+  uint64_t         n;
+  uint32_t const * set_first;  /* [n_set+1]                                 */
+  uint64_t         n_set;
+  uint8_t const *  tab;        /* fd_reedsol_core_tables's block, 16-B aligned */
+  int8_t *         set_out;    /* [n_set] out: 0, ERR_PARSE, UNSUPPORTED, ERR_SET, ERR_PARTIAL, ERR_CORRUPT */
+} fd_ed25519_fec_recover_params_t;
+
+int fd_ed25519_hip_launch_fec_recover( fd_ed25519_fec_recover_params_t const * p, void * stream );
+
 /* ---- generator (fd_ed25519_gen.hip) ---- */
 
 typedef struct {

@@ -30,7 +30,7 @@ struct fd_ed25519_hip_engine {
   int32_t *    d_btab16;     /* [0..2^15]B, the verify kernels' wide B table  */
   int32_t *    btabw[2];    /* shared per device: [0..2^24)B, [0..2^24)[2^144]B */
   int32_t *    btabs[2][8]; /* shared per device: dsm16s<4>'s and <8>'s compact tables, when acquired */
-  uint8_t *    d_rstab;     /* the parity kernel's product and coefficient tables (fd_reedsol_core.h) */
+  uint8_t *    d_rstab;     /* the parity and recover kernels' tables (fd_reedsol_core.h) */
   /* Pipeline lanes: the per-chunk scratch of a chunk in flight, and the
      streams its phases run on.  Lane 0 runs on the caller's stream (or the
      engine's); the chunks of a multi-chunk call alternate between lane 0

@@ -1,8 +1,8 @@
 /* fd_ed25519_hip_fronts.c -- the fronts before the verify phases
-   (include/fd_ed25519_hip.h Parts 2b-2g): stage kernel, verify_common,
+   (include/fd_ed25519_hip.h Parts 2b-2h): stage kernel, verify_common,
    finish kernel in a *_dev; pack, upload, *_dev, download, synchronise in a
    *_host ("The shape of a front"); and the rules the stage
-   kernels run, on the host (*_count, *_plan, *_root, fec_parity).  Part of the engine:
+   kernels run, on the host (*_count, *_plan, *_root, fec_parity, fec_recover).  Part of the engine:
    the *_host wrappers stage in its pinned buffers
    (fd_ed25519_hip_engine_fields.h). */
 
@@ -762,3 +762,123 @@ fd_ed25519_hip_fec_parity_host( fd_ed25519_hip_engine_t * e, unsigned long n, un
   }
   return FD_ED25519_HIP_OK;
 }
+
+/* ---- recovering received FEC sets (include/fd_ed25519_hip.h Part 2h) -- */
+
+_Static_assert( FD_ED25519_HIP_FEC_ERR_PARTIAL==FD_REEDSOL_CORE_ERR_PARTIAL &&
+                FD_ED25519_HIP_FEC_ERR_CORRUPT==FD_REEDSOL_CORE_ERR_CORRUPT, "public and core recover codes differ" );
+
+/* the rules and the code the recover kernel runs, on the host (no GPU) */
+int
+fd_ed25519_hip_fec_recover( unsigned char * shreds, unsigned long const * shred_off, unsigned int const * shred_sz,
+                            unsigned char const * erased, unsigned long cnt ) {
+  return fd_reedsol_core_recover( shreds, shred_off, shred_sz, erased, cnt );
+}
+
+int
+fd_ed25519_hip_fec_recover_dev( fd_ed25519_hip_engine_t * e, unsigned long n, unsigned char * shreds,
+                                unsigned long const * shred_off, unsigned int const * shred_sz, unsigned char const * erased,
+                                unsigned long n_set, unsigned int const * set_first, signed char * set_out, void * stream ) {
+  hipStream_t st;
+  int err = front_begin( e, n_set, set_first && set_out && ( !n || ( shreds && shred_off && shred_sz && erased ) ) &&
+                                   n<=UINT32_MAX && n_set<=INT32_MAX, (uintptr_t)shreds, "shreds", stream, &st );
+  if( err<=0 ) return err;
+  fd_ed25519_fec_recover_params_t rp = { 0 };
+  rp.shreds = shreds; rp.shred_off = (uint64_t const *)shred_off; rp.shred_sz = shred_sz; rp.erased = erased; rp.n = n;
+  rp.set_first = set_first; rp.n_set = n_set; rp.tab = e->d_rstab; rp.set_out = (int8_t *)set_out;
+  HIPCHK( (hipError_t)fd_ed25519_hip_launch_fec_recover( &rp, st ), "fec_recover launch" );
+  return FD_ED25519_HIP_OK;
+}
+
+/* Pass by pass, whole sets at a time, as fec_parity_host.  A pass's staging,
+   the same on the host and on the device: the received slots back to back
+   (capped at FD_SHRED_MAX_SZ as the seal's), then, from the next 16-byte
+   boundary, the erased slots 1228 bytes apart, of which nothing goes up --
+   the kernel reads an erased slot's size alone -- and all comes down.
+   in: off u64 [m], set_first u32 [ms+1], sz u32 [m], erased u8 [m]; out:
+   codes [ms].  Of a set with code 0 the bytes rule 12 names of its erased
+   slots are copied back, nothing else. */
+int
+fd_ed25519_hip_fec_recover_host( fd_ed25519_hip_engine_t * e, unsigned long n, unsigned char * shreds,
+                                 unsigned long const * shred_off, unsigned int const * shred_sz, unsigned char const * erased,
+                                 unsigned long n_set, unsigned int const * set_first, signed char * set_out ) {
+  hipStream_t st;
+  int err = front_begin( e, n_set, set_first && set_out && ( !n || ( shreds && shred_off && shred_sz && erased ) ) &&
+                                   n<=UINT32_MAX, 0UL, NULL, NULL, &st );
+  if( err<=0 ) return err;
+  for( uint64_t k0=0UL; k0<n_set; ) {
+    uint64_t k1 = k0, m = 0UL;
+    for( ; k1<n_set && k1-k0<FRONT_HOST_CHUNK; k1++ ) {
+      uint64_t first = set_first[k1], last = set_first[k1+1UL];
+      uint64_t cnt = ( first<=last && last<=n && last-first<=FD_FEC_CORE_CNT_MAX ) ? last-first : 0UL;
+      if( m+cnt>FRONT_HOST_CHUNK ) break;
+      m += cnt;
+    }
+    uint64_t ms = k1-k0;
+    uint64_t first_at = 8UL*m, sz_at = first_at + 4UL*( ms+1UL ), er_at = sz_at + 4UL*m, in_bytes = er_at + m;
+    if( (err = front_room( e, m*FD_SHRED_CORE_MAX_SZ + 16UL, in_bytes, ms )) ) return err;
+    uint64_t * h_off   = (uint64_t *)e->h_fr_in;
+    uint32_t * h_first = (uint32_t *)( e->h_fr_in + first_at );
+    uint32_t * h_sz    = (uint32_t *)( e->h_fr_in + sz_at );
+    uint8_t *  h_er    = e->h_fr_in + er_at;
+    /* the received slots first: where they end, the erased slots begin */
+    uint64_t whole = 0UL, i = 0UL;
+    for( uint64_t k=k0; k<k1; k++ ) {
+      uint64_t first = set_first[k], last = set_first[k+1UL];
+      uint64_t cnt = ( first<=last && last<=n && last-first<=FD_FEC_CORE_CNT_MAX ) ? last-first : 0UL;
+      for( uint64_t j=first; j<first+cnt; j++ )
+        if( !erased[j] ) whole += shred_sz[j]<=FD_SHRED_CORE_MAX_SZ ? shred_sz[j] : FD_SHRED_CORE_MAX_SZ;
+    }
+    uint64_t er_base = ( whole+15UL ) & ~15UL, pos = 0UL, n_er = 0UL;
+    for( uint64_t k=k0; k<k1; k++ ) {
+      uint64_t first = set_first[k], last = set_first[k+1UL];
+      uint64_t cnt = ( first<=last && last<=n && last-first<=FD_FEC_CORE_CNT_MAX ) ? last-first : 0UL;
+      h_first[ k-k0 ] = (uint32_t)i;
+      for( uint64_t j=first; j<first+cnt; j++, i++ ) {
+        h_sz[i] = shred_sz[j];
+        h_er[i] = erased[j]!=0U;
+        if( erased[j] ) {
+          h_off[i] = er_base + FD_SHRED_CORE_MAX_SZ*n_er++;
+        } else {
+          uint64_t cp = shred_sz[j]<=FD_SHRED_CORE_MAX_SZ ? shred_sz[j] : FD_SHRED_CORE_MAX_SZ;
+          if( cp ) memcpy( e->h_msgs + pos, shreds + shred_off[j], cp );
+          h_off[i] = pos;
+          pos += cp;
+        }
+      }
+    }
+    h_first[ ms ] = (uint32_t)i;
+    if( (err = front_upload( e, pos, in_bytes, st )) ) return err;
+    err = fd_ed25519_hip_fec_recover_dev( e, m, e->d_msgs, (unsigned long const *)e->d_fr_in,
+                                          (unsigned int const *)( e->d_fr_in + sz_at ), e->d_fr_in + er_at, ms,
+                                          (unsigned int const *)( e->d_fr_in + first_at ), (signed char *)e->d_fr_out, st );
+    if( err ) return err;
+    if( n_er )
+      HIPCHK( hipMemcpyAsync( e->h_msgs + er_base, e->d_msgs + er_base, FD_SHRED_CORE_MAX_SZ*n_er, hipMemcpyDeviceToHost, st ),
+              "D2H recovered shreds" );
+    if( (err = front_download( e, ms, st )) ) return err;
+    memcpy( set_out + k0, e->h_fr_out, ms );
+    for( uint64_t k=k0; k<k1; k++ ) {
+      if( set_out[k] ) continue;                      /* rule 12 */
+      uint64_t first = set_first[k], cnt = set_first[k+1UL]-first;
+      uint64_t region = FD_REEDSOL_CORE_REGION( fd_fec_core_depth( (unsigned)cnt ) );
+      /* code 0: a received code shred has passed the rules, and its data_cnt is the set's */
+      uint64_t d = cnt;
+      for( uint64_t j=0UL; j<cnt; j++ )
+        if( !erased[ first+j ] && ( shreds[ shred_off[ first+j ] + 0x40UL ] & 0xf0 )==0x40 ) {
+          d = fd_shred_core_u16( shreds + shred_off[ first+j ] + 0x53UL );
+          break;
+        }
+      for( uint64_t j=0UL; j<cnt; j++ ) {
+        if( !erased[ first+j ] ) continue;            /* a received slot: read only */
+        unsigned char const * from = e->h_msgs + h_off[ h_first[ k-k0 ]+j ];
+        unsigned char *       to   = shreds + shred_off[ first+j ];
+        if( j<d ) { memcpy( to, from, 64UL ); memcpy( to + 0x40UL, from + 0x40UL, region ); }
+        else      memcpy( to, from, FD_SHRED_CORE_CODE_HDR_SZ + region );
+      }
+    }
+    k0 = k1;
+  }
+  return FD_ED25519_HIP_OK;
+}
+

@@ -230,6 +230,31 @@ def fec_parity(shreds):
     return code, [buf[int(off[i]):int(off[i]) + int(sz[i])].tobytes() for i in range(cnt)]
 
 
+# recovering received FEC sets (include/fd_ed25519_hip.h Part 2h)
+FEC_ERR_PARTIAL = -23
+FEC_ERR_CORRUPT = -24
+_lib.fd_ed25519_hip_fec_recover.argtypes = [_u8p] * 4 + [ctypes.c_ulong]
+_lib.fd_ed25519_hip_fec_recover_dev.argtypes = [ctypes.c_void_p, ctypes.c_ulong] + [_u8p] * 4 + [ctypes.c_ulong] + [_u8p] * 3
+_lib.fd_ed25519_hip_fec_recover_host.argtypes = [ctypes.c_void_p, ctypes.c_ulong] + [_u8p] * 4 + [ctypes.c_ulong] + [_u8p] * 2
+
+
+def fec_recover(shreds, erased):
+    """fd_ed25519_hip_fec_recover: (code, the slots after the call) of one
+    FEC set given as its slots in tree order, erased[j] nonzero where slot j
+    is erased (its bytes are not read, its length is its size) -- the erased
+    slots' signatures, code headers and protected regions filled when the
+    code is 0, nothing changed otherwise (host only)."""
+    from .tile import pack_payloads
+    cnt = len(shreds)
+    if not cnt:
+        return _lib.fd_ed25519_hip_fec_recover(None, None, None, None, 0), []
+    buf, off, sz = pack_payloads([bytes(s) for s in shreds])
+    er = _c([1 if x else 0 for x in erased], np.uint8)
+    assert len(er) == cnt
+    code = _lib.fd_ed25519_hip_fec_recover(_ptr(buf), _ptr(off), _ptr(sz), _ptr(er), cnt)
+    return code, [buf[int(off[i]):int(off[i]) + int(sz[i])].tobytes() for i in range(cnt)]
+
+
 # signed gossip and repair control packets (include/fd_ed25519_hip.h Part 2d)
 PROTO_GOSSIP = 0
 PROTO_REPAIR_SERV = 1
@@ -614,6 +639,39 @@ class Engine:
         """Device-resident fd_ed25519_hip_fec_parity_dev: device addresses (ints); async."""
         _check(_lib.fd_ed25519_hip_fec_parity_dev(self._h, int(n), d_shreds, d_off, d_sz, int(n_set), d_set_first, d_set_out,
                                                   stream))
+
+    def fec_recover_flat(self, shreds, erased, set_first):
+        """fd_ed25519_hip_fec_recover_host on shreds (a list of slots) whose
+        set k is shreds[set_first[k]:set_first[k + 1]] in tree order, erased
+        one flag per slot -> (int8 code per set, the slots after the call);
+        synchronous."""
+        from .tile import pack_payloads
+        n, n_set = len(shreds), len(set_first) - 1
+        first = _c(set_first, np.uint32)
+        codes = np.zeros(max(1, n_set), np.int8)
+        er = _c([1 if x else 0 for x in erased] + [0], np.uint8)
+        assert len(er) == n + 1
+        buf, off, sz = pack_payloads([bytes(s) for s in shreds]) if n else (np.zeros(1, np.uint8),) * 3
+        _check(_lib.fd_ed25519_hip_fec_recover_host(self._h, n, _ptr(buf), _ptr(off), _ptr(sz), _ptr(er), n_set, _ptr(first),
+                                                    _ptr(codes)))
+        return codes[:n_set], [buf[int(off[i]):int(off[i]) + int(sz[i])].tobytes() for i in range(n)]
+
+    def fec_recover_host(self, sets, erased):
+        """Recovers received FEC sets (fd_ed25519_hip_fec_recover_host): sets
+        is a list of sets, each the list of its slots in tree order, erased
+        the list of each set's flags (nonzero: the slot is erased and only
+        its length counts) -> (int8 code per set, the sets with the erased
+        slots filled where the code is 0); synchronous."""
+        first = [0]
+        for s in sets:
+            first.append(first[-1] + len(s))
+        codes, flat = self.fec_recover_flat([x for s in sets for x in s], [x for e in erased for x in e], first)
+        return codes, [flat[first[k]:first[k + 1]] for k in range(len(sets))]
+
+    def fec_recover_dev(self, n, d_shreds, d_off, d_sz, d_erased, n_set, d_set_first, d_set_out, stream=None):
+        """Device-resident fd_ed25519_hip_fec_recover_dev: device addresses (ints); async."""
+        _check(_lib.fd_ed25519_hip_fec_recover_dev(self._h, int(n), d_shreds, d_off, d_sz, d_erased, int(n_set), d_set_first,
+                                                   d_set_out, stream))
 
     # ---- batched signing / synthetic workloads -------------------------
     def sign_dev(self, n, d_msgs, d_off, d_sz, d_privs, d_sigs, d_pubs, stream=None):

@@ -214,7 +214,9 @@ typedef struct fd_ed25519_hip_engine fd_ed25519_hip_engine_t;
    Merkle shreds; 13: Part 2d, signed gossip and repair control packets; 14:
    Part 2e, the CRDS values of gossip pull responses and push messages; 15:
    Part 2f, sealing a leader's FEC sets; 16: Part 2g, the Reed-Solomon
-   parity of a leader's FEC sets).
+   parity of a leader's FEC sets; still 16 with Part 2h, recovering received
+   FEC sets: it only adds entry points and two codes, and nothing a consumer
+   of version 16 was built against has changed).
    A consumer checks
    the library it loaded against the header it was built with:
    fd_ed25519_hip_abi_check( FD_ED25519_HIP_ABI_VERSION,
@@ -1176,6 +1178,115 @@ fd_ed25519_hip_fec_parity_host( fd_ed25519_hip_engine_t * engine,
                                 unsigned long             n_set,
                                 unsigned int const *      set_first,
                                 signed char *             set_out );
+
+/* ---- Part 2h: recovering received FEC sets ------------------------------ */
+
+/* The other direction of Part 2g, the step every validator but the leader
+   runs on every FEC set: the second half of fd_fec_resolver_add_shred
+   (src/disco/shred/fd_fec_resolver.c:474-594).  Once data_cnt shreds of a
+   set are in, the resolver regenerates the missing ones
+   (fd_reedsol_recover_fini), fills their signatures and headers, rebuilds
+   the tree and keeps the set only if everything agrees.  The entry points
+   below do the first two steps; followed by Part 2f without keys (which
+   writes the proofs and leaves the signatures alone) and Part 2c under the
+   leader's key over the same arrays, they are the resolver from line 474
+   on: Part 2c gives 0 for every shred exactly when the rebuilt tree's root
+   is the one the leader signed.
+
+   A set is cnt = d + p slots in tree order, each shred_sz[j] bytes at
+   shred_off[j], with one erased byte per slot: 0, the slot holds a received
+   shred; nonzero, it is erased and nothing of it is read.  The first d
+   received slots in set order are the basis (as in fd_reedsol_recover_fini)
+   and determine the protected region (Part 2g) of every other slot: an
+   erased one is written, a received one is compared.
+
+   A received slot is judged as in Part 2f.  d is the data_cnt of the set's
+   first received code shred that passes Part 2f's rules (no header byte is
+   read that the parser has not proved present).  The first failing slot in
+   set order decides:
+   an erased slot of fewer than 1203 bytes at a place below d, or fewer than
+   1228 at or behind it, gets FEC_ERR_PARSE; a received data shred at a place
+   >= d, and a received code shred whose data_cnt is not d or whose code_cnt
+   is not cnt - d, get FEC_ERR_SET.  Then the set: no received code shred,
+   FEC_ERR_SET (the resolver learns data_cnt only from one); fewer than d
+   received, FEC_ERR_PARTIAL; a received slot beyond the basis that differs
+   from its recomputed region in any byte, FEC_ERR_CORRUPT; then, on the set
+   as it would stand (fd_fec_resolver.c:546-572), a recovered data shred
+   that Part 2f's rules do not pass at its place, a data shred whose slot,
+   version, fec_set_idx or parent_off is not data shred 0's, and a received
+   code shred whose slot, version or fec_set_idx is not data shred 0's,
+   FEC_ERR_SET.
+
+   A set with a nonzero code has no byte of any slot written.  In a set with
+   code 0 nothing of a received slot is written; an erased data slot gets
+   bytes [0, 64), the signature of the set's first received shred (which the
+   caller has verified with Part 2c), and [0x40, 0x40 + P); an erased code
+   slot d + i gets [0, 64) likewise, the header of fd_fec_resolver.c:515-524
+   in [0x40, 0x59) -- variant 0x40 | depth; slot, version and fec_set_idx of
+   the first received code shred; idx = that shred's idx - its code.idx + i;
+   data_cnt d, code_cnt p, code.idx i -- and [0x59, 0x59 + P).  The proof
+   bytes are Part 2f's; bytes beyond 1203 or 1228 of a larger slot are not
+   written.
+
+   Out of scope: the resolver's bookkeeping (the sets in progress,
+   duplicates, eviction), a combined recover + tree + verify entry point,
+   chained and resigned variants, and error correction, which the reference
+   does not do either. */
+#define FD_ED25519_HIP_FEC_ERR_PARTIAL (-23)   /* fewer shreds received than the set has data shreds */
+#define FD_ED25519_HIP_FEC_ERR_CORRUPT (-24)   /* a received shred is not on the polynomial of the first d */
+
+/* One set, host only (no GPU), from the same source as the device's kernel.
+   Slots do not overlap; erased is cnt bytes.  Returns 0 with the set's
+   erased slots written in place as said above, else the set's code with
+   nothing written. */
+int
+fd_ed25519_hip_fec_recover( unsigned char *       shreds,
+                            unsigned long const * shred_off,
+                            unsigned int const *  shred_sz,
+                            unsigned char const * erased,
+                            unsigned long         cnt );
+
+/* Device-resident batch: every pointer but the engine is a device pointer,
+   with fd_ed25519_hip_fec_seal_dev's rules for them: slot i is
+   shreds[shred_off[i] .. shred_off[i] + shred_sz[i]) and may start at any
+   byte; slots do not overlap; the buffer starts 16-byte aligned and stays
+   readable at least 16 bytes past the end of the last slot; erased is n
+   bytes; set k is the slots [set_first[k], set_first[k+1]) in tree order,
+   and a range that runs backwards or leaves [0, n) gets FEC_ERR_SET and
+   touches nothing.  n < 2^32, n_set < 2^31.  set_out[k] receives the set's
+   code.
+
+   Asynchronous on `stream` (NULL: the engine's): one launch, whose tables
+   the engine made when it was created; no workspace, no allocation, no
+   synchronisation.  n_set==0 is a no-op. */
+int
+fd_ed25519_hip_fec_recover_dev( fd_ed25519_hip_engine_t * engine,
+                                unsigned long             n,
+                                unsigned char *           shreds,
+                                unsigned long const *     shred_off,
+                                unsigned int const *      shred_sz,
+                                unsigned char const *     erased,
+                                unsigned long             n_set,
+                                unsigned int const *      set_first,
+                                signed char *             set_out,
+                                void *                    stream );
+
+/* Host-buffer batch, synchronous: packs whole sets into pinned staging
+   memory (in passes, so any n fits) -- a received shred travels whole, an
+   erased slot as its size alone --, copies, runs fec_recover_dev and copies
+   back set_out[0..n_set) and, into the caller's erased slots of every set
+   with code 0, the bytes named above -- nothing else.  No alignment is asked
+   of any argument. */
+int
+fd_ed25519_hip_fec_recover_host( fd_ed25519_hip_engine_t * engine,
+                                 unsigned long             n,
+                                 unsigned char *           shreds,
+                                 unsigned long const *     shred_off,
+                                 unsigned int const *      shred_sz,
+                                 unsigned char const *     erased,
+                                 unsigned long             n_set,
+                                 unsigned int const *      set_first,
+                                 signed char *             set_out );
 
 /* ---- Part 3: batched signing and the synthetic workload generator ------ */
 
