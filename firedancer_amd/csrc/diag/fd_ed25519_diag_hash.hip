@@ -27,7 +27,8 @@
    buf_sz above 2^28 (SHA-256 keeps the bit length in one word), a missing
    pointer, and any case whose bytes do not lie inside [0, buf_sz): off + sz
    (SHA256_BYTES: sz >= 1 too), off + 64 + sz for the leaf (sz >= 38), off +
-   20 for the node.  No case can therefore read outside the allocation:
+   20 for the node, off + 64 for SHA256_LEAF65; SHA256_CHAIN32: sz above
+   4096.  No case can therefore read outside the allocation:
    the loaders read aligned 16-byte granules from the dword that holds a
    message's first byte to at most 15 bytes past its last (the allocation
    is 256-byte aligned), sha256_node_load the six dwords around the 20
@@ -50,6 +51,13 @@
                       5..7 are not part of it), the sibling the 20 bytes at
                       buf + off, right = flag & 1
      SHA256_NODE_PAIR sha256_node_pair( left = operand[0..5), right = operand[5..10) )
+   and, through fd_ed25519_diag_poh_hash( op 0..3, the same arguments ), the
+   proof-of-history hashes (fd_ed25519_poh.hip's):
+
+     SHA256_LEAF65    sha256_leaf65( buf + off ): SHA-256( 0x00 || buf[off, off+64) )
+     SHA256_NODE65    sha256_node65( left = operand[0..8), right = operand[8..16) )
+     SHA256_CHAIN32   sz times sha256_chain32 on the state operand[0..8), sz <= 4096
+     SHA256_MIX64     sha256_mix64( state = operand[0..8), root = operand[8..16) )
 
    with m = buf[off, off + sz) as the product builds a sha_msg_src: base the
    aligned dword holding byte off, shift = (buf + off) & 3 = off & 3.
@@ -90,7 +98,9 @@
 
 enum {
   HASH_OP_SHA512_PRE8, HASH_OP_SHA512_RAM, HASH_OP_SHA512_RAM_2W, HASH_OP_SHA256_BYTES, HASH_OP_SHA256_LEAF,
-  HASH_OP_SHA256_NODE, HASH_OP_SHA256_NODE_PAIR, HASH_OP_N
+  HASH_OP_SHA256_NODE, HASH_OP_SHA256_NODE_PAIR, HASH_OP_N,
+  /* fd_ed25519_diag_poh_hash's ops 0..3, behind the first entry point's */
+  HASH_OP_SHA256_LEAF65 = HASH_OP_N, HASH_OP_SHA256_NODE65, HASH_OP_SHA256_CHAIN32, HASH_OP_SHA256_MIX64, HASH_OP_END
 };
 
 FD_DEV void diag_msg(sha_msg_src& m, const uint8_t* buf, const uint32_t* src) {
@@ -144,6 +154,25 @@ __global__ void __launch_bounds__(64) diag_hash_kernel(const uint8_t* buf, const
       for (int w = 0; w < 5; w++) { l[w] = x[w]; r[w] = x[5 + w]; }
       sha256_node_pair(h, l, r);
     }
+    if (OP == HASH_OP_SHA256_LEAF65) sha256_leaf65(h, s);
+    if (OP == HASH_OP_SHA256_NODE65 || OP == HASH_OP_SHA256_MIX64) {
+      uint32_t l[8], r[8];
+#pragma unroll
+      for (int w = 0; w < 8; w++) { l[w] = x[w]; r[w] = x[8 + w]; }
+      if (OP == HASH_OP_SHA256_NODE65) {
+        sha256_node65(h, l, r);
+      } else {
+#pragma unroll
+        for (int w = 0; w < 8; w++) h[w] = l[w];
+        sha256_mix64(h, r);
+      }
+    }
+    if (OP == HASH_OP_SHA256_CHAIN32) {
+#pragma unroll
+      for (int w = 0; w < 8; w++) h[w] = x[w];
+#pragma clang loop unroll(disable)
+      for (uint32_t t = 0; t < src[1]; t++) sha256_chain32(h);
+    }
 #pragma unroll
     for (int w = 0; w < 8; w++) o[w] = h[w];
   }
@@ -191,7 +220,8 @@ typedef void (*diag_hash_kernel_t)(const uint8_t*, const uint32_t*, uint32_t*, u
 static diag_hash_kernel_t hash_kernel(int op) {
   switch (op) {
     K(HASH_OP_SHA512_PRE8) K(HASH_OP_SHA512_RAM) K(HASH_OP_SHA256_BYTES) K(HASH_OP_SHA256_LEAF) K(HASH_OP_SHA256_NODE)
-    K(HASH_OP_SHA256_NODE_PAIR)
+    K(HASH_OP_SHA256_NODE_PAIR) K(HASH_OP_SHA256_LEAF65) K(HASH_OP_SHA256_NODE65) K(HASH_OP_SHA256_CHAIN32)
+    K(HASH_OP_SHA256_MIX64)
   case HASH_OP_SHA512_RAM_2W: return diag_hash2w_kernel;
   default: return nullptr;
   }
@@ -208,12 +238,16 @@ static bool hash_case_ok(int op, const uint32_t* c, unsigned long buf_sz) {
   case HASH_OP_SHA256_LEAF: return sz >= 38u && off + 64u + sz <= buf_sz;
   case HASH_OP_SHA256_NODE: return off + 20u <= buf_sz;
   case HASH_OP_SHA256_NODE_PAIR: return true;   /* no bytes */
+  case HASH_OP_SHA256_LEAF65: return off + 64u <= buf_sz;
+  case HASH_OP_SHA256_NODE65:
+  case HASH_OP_SHA256_MIX64: return true;       /* no bytes */
+  case HASH_OP_SHA256_CHAIN32: return sz <= 4096u;   /* no bytes; sz is the number of compressions */
   default: return false;
   }
 }
 
-extern "C" int fd_ed25519_diag_hash(int op, const uint8_t* buf, unsigned long buf_sz, const uint32_t* in, uint32_t* out,
-                                    unsigned long n) {
+static int diag_hash_run(int op, const uint8_t* buf, unsigned long buf_sz, const uint32_t* in, uint32_t* out,
+                         unsigned long n) {
   const diag_hash_kernel_t kern = hash_kernel(op);
   if (!kern || !in || !out || n > DIAG_MAX_N || buf_sz > DIAG_MAX_BUF || (!buf && buf_sz)) return (int)hipErrorInvalidValue;
   for (unsigned long i = 0; i < n; i++)
@@ -255,4 +289,18 @@ extern "C" int fd_ed25519_diag_hash(int op, const uint8_t* buf, unsigned long bu
   if (d_in) (void)hipFree(d_in);
   if (d_out) (void)hipFree(d_out);
   return (int)e;
+}
+
+extern "C" int fd_ed25519_diag_hash(int op, const uint8_t* buf, unsigned long buf_sz, const uint32_t* in, uint32_t* out,
+                                    unsigned long n) {
+  if (op < 0 || op >= HASH_OP_N) return (int)hipErrorInvalidValue;
+  return diag_hash_run(op, buf, buf_sz, in, out, n);
+}
+
+/* the proof-of-history hashes: op 0 SHA256_LEAF65, 1 SHA256_NODE65, 2 SHA256_CHAIN32, 3 SHA256_MIX64; everything
+   else as fd_ed25519_diag_hash */
+extern "C" int fd_ed25519_diag_poh_hash(int op, const uint8_t* buf, unsigned long buf_sz, const uint32_t* in, uint32_t* out,
+                                        unsigned long n) {
+  if (op < 0 || op >= HASH_OP_END - HASH_OP_N) return (int)hipErrorInvalidValue;
+  return diag_hash_run(HASH_OP_N + op, buf, buf_sz, in, out, n);
 }

@@ -691,6 +691,40 @@ typedef struct {
 
 int fd_ed25519_hip_launch_fec_recover( fd_ed25519_fec_recover_params_t const * p, void * stream );
 
+/* ---- a block's proof-of-history hash chain (fd_ed25519_poh.hip) ---- */
+
+/* One parameter block for the three launches (fd_poh_core.h's rules):
+   leaf   lane j < n_sig: leaves[j] = SHA-256( 0x00 || sig j ), zeros for a
+          signature that leaves the buffer
+   tree   workgroup i < n: roots[i] = the root of leaves [sig_first[i],
+          sig_first[i+1]), reduced in place; pre[i] = 1 if a signature of the
+          range leaves the buffer, else 0; nothing but pre[i] = 0 for a range
+          that is empty, runs backwards or leaves [0, n_sig)
+   chain  lane i < n: the judge, the k compressions, the mixin with roots[i],
+          the comparison; out[i] and, if asked for, out_hash[i]
+   tools/poh_bench.py mirrors this struct field for field (its Params): change both together. */
+typedef struct {
+  uint8_t const *  buf;        /* readable 16 B past buf_sz                 */
+  uint64_t         buf_sz;
+  uint64_t const * hdr_off;    /* [n]                                       */
+  uint64_t const * in_off;     /* [n]                                       */
+  uint32_t const * sig_first;  /* [n+1]                                     */
+  uint64_t const * sig_off;    /* [n_sig]                                   */
+  uint64_t         n;
+  uint64_t         n_sig;
+  uint64_t         hash_cnt_max;
+  uint32_t *       leaves;     /* work: [n_sig][8] big-endian hash words    */
+  uint32_t *       roots;      /* work: [n][8]                              */
+  int8_t *         pre;        /* work: [n]                                 */
+  int8_t *         out;        /* [n] out: 0, POH_ERR_PARSE, POH_UNSUPPORTED, POH_ERR_HASH */
+  uint8_t *        out_hash;   /* [n][32] out, or NULL; 16-byte aligned     */
+} fd_ed25519_poh_params_t;
+
+int fd_ed25519_hip_launch_poh_leaf ( fd_ed25519_poh_params_t const * p, void * stream );
+int fd_ed25519_hip_launch_poh_tree ( fd_ed25519_poh_params_t const * p, void * stream );
+int fd_ed25519_hip_launch_poh_chain( fd_ed25519_poh_params_t const * p, void * stream );
+unsigned fd_ed25519_hip_private_poh_params_bytes( void );   /* sizeof(fd_ed25519_poh_params_t), for tools/poh_bench.py */
+
 /* ---- generator (fd_ed25519_gen.hip) ---- */
 
 typedef struct {

@@ -3,7 +3,8 @@
    out of the caller's 16-byte-aligned buffer.  Plain C11, host only, nothing
    but pointer arithmetic: the engine (host/fd_ed25519_hip_fronts.c) takes
    its kernels' arrays from here, and tests/front_work_main.c (the CRDS
-   front's: tests/crds_work_main.c, the FEC seal's: tests/fec_work_main.c) holds every layout to the public
+   front's: tests/crds_work_main.c, the FEC seal's: tests/fec_work_main.c, the proof-of-history check's:
+   tests/poh_work_main.c) holds every layout to the public
    FD_ED25519_HIP_*_WORK_BYTES macro a caller sizes the buffer with.  A layout has no padding: the elements only get smaller, so
    every array is aligned to its element at any count. */
 #ifndef FD_FRONT_WORK_H
@@ -105,6 +106,26 @@ front_work_fec( void * work, uint64_t n, uint64_t n_set, front_work_t * w ) {
   w->msg_off = (uint64_t *)front_carve( &c, n_set, 8UL );
   w->msg_sz  = (uint32_t *)front_carve( &c, n_set, 4UL );
   w->set_of  = (uint32_t *)front_carve( &c, n,     4UL );
+  return (uint64_t)( c - (uint8_t *)work );
+}
+
+/* The proof-of-history check (fd_ed25519_hip_poh_dev) has no verify phases
+   either: the leaf hashes, which the tree kernel reduces in place, [n_sig]
+   rows of eight words; the roots, [n] rows; and the tree's flag per
+   microblock (a signature that leaves the buffer).  tools/poh_bench.py
+   repeats this order (Batch.params): change both together. */
+typedef struct {
+  uint32_t * leaves;
+  uint32_t * roots;
+  int8_t *   pre;
+} front_work_poh_t;
+
+static inline uint64_t
+front_work_poh( void * work, uint64_t n, uint64_t n_sig, front_work_poh_t * w ) {
+  uint8_t * c = (uint8_t *)work;
+  w->leaves = (uint32_t *)front_carve( &c, n_sig, 32UL );
+  w->roots  = (uint32_t *)front_carve( &c, n,     32UL );
+  w->pre    = (int8_t *)  front_carve( &c, n,     1UL );
   return (uint64_t)( c - (uint8_t *)work );
 }
 

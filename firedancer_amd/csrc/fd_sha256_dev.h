@@ -281,3 +281,143 @@ FD_DEV void sha256_shred_root(uint32_t (&h)[8], const uint8_t* s, const fd_shred
     sha256_node(h, cur, (c.shred_idx >> l) & 1u);
   }
 }
+
+/* ---- the proof-of-history hashes (fd_poh_core.h, fd_ed25519_poh.hip) ----
+
+   Four fixed-size messages: the chain step SHA-256( state[32] ), the mixin
+   SHA-256( state[32] || root[32] ), and the two hashes of the signature
+   tree, SHA-256( 0x00 || sig[64] ) and SHA-256( 0x01 || left[32] ||
+   right[32] ).  Padding and lengths are compile-time constants. */
+
+/* the round constants as literals: where the index is a compile-time constant
+   (an unrolled round) the compiler adds them to constant schedule words */
+FD_DEV constexpr uint32_t sha256_k_lit(int i) {
+  constexpr uint32_t k[64] = {
+    0x428a2f98u, 0x71374491u, 0xb5c0fbcfu, 0xe9b5dba5u, 0x3956c25bu, 0x59f111f1u, 0x923f82a4u, 0xab1c5ed5u,
+    0xd807aa98u, 0x12835b01u, 0x243185beu, 0x550c7dc3u, 0x72be5d74u, 0x80deb1feu, 0x9bdc06a7u, 0xc19bf174u,
+    0xe49b69c1u, 0xefbe4786u, 0x0fc19dc6u, 0x240ca1ccu, 0x2de92c6fu, 0x4a7484aau, 0x5cb0a9dcu, 0x76f988dau,
+    0x983e5152u, 0xa831c66du, 0xb00327c8u, 0xbf597fc7u, 0xc6e00bf3u, 0xd5a79147u, 0x06ca6351u, 0x14292967u,
+    0x27b70a85u, 0x2e1b2138u, 0x4d2c6dfcu, 0x53380d13u, 0x650a7354u, 0x766a0abbu, 0x81c2c92eu, 0x92722c85u,
+    0xa2bfe8a1u, 0xa81a664bu, 0xc24b8b70u, 0xc76c51a3u, 0xd192e819u, 0xd6990624u, 0xf40e3585u, 0x106aa070u,
+    0x19a4c116u, 0x1e376c08u, 0x2748774cu, 0x34b0bcb5u, 0x391c0cb3u, 0x4ed8aa4au, 0x5b9cca4fu, 0x682e6ff3u,
+    0x748f82eeu, 0x78a5636fu, 0x84c87814u, 0x8cc70208u, 0x90befffau, 0xa4506cebu, 0xbef9a3f7u, 0xc67178f2u,
+  };
+  return k[i];
+}
+
+/* the small sigmas in plain C: of a constant word they fold to a constant */
+FD_DEV constexpr uint32_t sha256_s0_c(uint32_t x) { return ((x >> 7) | (x << 25)) ^ ((x >> 18) | (x << 14)) ^ (x >> 3); }
+FD_DEV constexpr uint32_t sha256_s1_c(uint32_t x) { return ((x >> 17) | (x << 15)) ^ ((x >> 19) | (x << 13)) ^ (x >> 10); }
+
+/* h <- SHA-256( h[0..8) as 32 bytes ), one compression (fd_poh_append's
+   step).  Schedule words 8..15 are the constants 0x80000000, 0, ..., 0, 0x100
+   and the state starts at the initial value: rounds 0..15 and schedule steps
+   16..31 are unrolled with literal constants, so the eight constant words
+   are never carried -- rounds 8..15 add one folded literal, steps 16..30 lose
+   the terms that are zero, and round 0 starts from constants.  Rounds 32..63
+   are the common loop. */
+FD_DEV void sha256_chain32(uint32_t (&h)[8]) {
+  uint32_t w[16];
+#pragma unroll
+  for (int i = 0; i < 8; i++) w[i] = h[i];
+  w[8] = 0x80000000u;
+#pragma unroll
+  for (int i = 9; i < 15; i++) w[i] = 0u;
+  w[15] = 0x100u;
+  uint32_t a = 0x6a09e667u, b = 0xbb67ae85u, c = 0x3c6ef372u, d = 0xa54ff53au;
+  uint32_t e = 0x510e527fu, f = 0x9b05688cu, g = 0x1f83d9abu, hh = 0x5be0cd19u;
+#pragma unroll
+  for (int r = 0; r < 32; r++) {
+    if (r >= 16) {
+      const uint32_t w15 = w[(r + 1) & 15], w2 = w[(r + 14) & 15];
+      w[r & 15] += sha256_s0_c(w15) + w[(r + 9) & 15] + sha256_s1_c(w2);
+    }
+    const uint32_t S1 = sha256_xor3(sha256_ror(e, 6), sha256_ror(e, 11), sha256_ror(e, 25));
+    const uint32_t t1 = hh + S1 + sha256_ch(e, f, g) + (sha256_k_lit(r) + w[r & 15]);
+    const uint32_t S0 = sha256_xor3(sha256_ror(a, 2), sha256_ror(a, 13), sha256_ror(a, 22));
+    const uint32_t mj = sha256_maj(a, b, c);
+    hh = g; g = f; f = e; e = d + t1; d = c; c = b; b = a; a = t1 + S0 + mj;
+  }
+  uint32_t v[8] = {a, b, c, d, e, f, g, hh};
+#pragma clang loop unroll(disable)
+  for (int r0 = 32; r0 < 64; r0 += 16) sha256_rounds16<true>(v, w, r0);
+  h[0] = 0x6a09e667u + v[0]; h[1] = 0xbb67ae85u + v[1]; h[2] = 0x3c6ef372u + v[2]; h[3] = 0xa54ff53au + v[3];
+  h[4] = 0x510e527fu + v[4]; h[5] = 0x9b05688cu + v[5]; h[6] = 0x1f83d9abu + v[6]; h[7] = 0x5be0cd19u + v[7];
+}
+
+/* h <- SHA-256( h[0..8) || root[0..8) ) (fd_poh_mixin): the data block, then
+   the padding block of a 64-byte message, all constants */
+FD_DEV void sha256_mix64(uint32_t (&h)[8], const uint32_t (&root)[8]) {
+  uint32_t w[16];
+#pragma unroll
+  for (int i = 0; i < 8; i++) { w[i] = h[i]; w[8 + i] = root[i]; }
+  sha256_init(h);
+  sha256_block(h, w);
+  w[0] = 0x80000000u;
+#pragma unroll
+  for (int t = 1; t < 15; t++) w[t] = 0u;
+  w[15] = 64u << 3;
+  sha256_block(h, w);
+}
+
+/* h = SHA-256( kind || x[0..16) as 64 bytes ), 65 bytes in two blocks: the
+   one-byte prefix puts the data one byte off the word grid, so stream word i
+   is the low byte of x[i-1] and the high three of x[i]; the second block is
+   the last data byte, the padding's 0x80, zeros and the length */
+FD_DEV void sha256_pre1_64(uint32_t (&h)[8], uint32_t kind, const uint32_t (&x)[16]) {
+  uint32_t w[16];
+  w[0] = (kind << 24) | (x[0] >> 8);
+#pragma unroll
+  for (int i = 1; i < 16; i++) w[i] = __builtin_amdgcn_alignbit(x[i - 1], x[i], 8);
+  const uint32_t last = (x[15] << 24) | 0x00800000u;
+  sha256_init(h);
+  sha256_block(h, w);
+  w[0] = last;
+#pragma unroll
+  for (int t = 1; t < 15; t++) w[t] = 0u;
+  w[15] = 65u << 3;
+  sha256_block(h, w);
+}
+
+/* the signature tree's node: h = SHA-256( 0x01 || left || right ), children
+   as big-endian words (fd_wbmtree32's branch, fd_bmtree's 32-byte node with
+   the 1-byte prefix) */
+FD_DEV void sha256_node65(uint32_t (&h)[8], const uint32_t (&left)[8], const uint32_t (&right)[8]) {
+  uint32_t x[16];
+#pragma unroll
+  for (int i = 0; i < 8; i++) { x[i] = left[i]; x[8 + i] = right[i]; }
+  sha256_pre1_64(h, 1u, x);
+}
+
+/* the signature tree's leaf: h = SHA-256( 0x00 || sig[0..64) ), sig at any
+   byte address, read as the shred leaf is: dword-aligned 16-byte loads (the
+   fifth only when sig is off the dword grid; it then reads up to 15 bytes
+   past the signature) realigned and byte-swapped by v_perm_b32 */
+FD_DEV void sha256_leaf65(uint32_t (&h)[8], const uint8_t* sig) {
+  const uintptr_t a = reinterpret_cast<uintptr_t>(sig);
+  sha256_src m;
+  m.base = reinterpret_cast<const uint32_t*>(a & ~(uintptr_t)3);
+  m.shift = (uint32_t)(a & 3);
+  m.total = 64u;
+  uint4 cur[SHA256_CHUNKS];
+  uint32_t x[16];
+  sha256_load_block(cur, m, 0u);
+  sha256_build_w<true>(x, cur, m, 0u, 1u);
+  sha256_pre1_64(h, 0u, x);
+}
+
+/* 32 bytes at any byte address as eight big-endian words: the nine aligned
+   dwords around them (the ninth only when off the dword grid; it then reads
+   up to 3 bytes past the field) */
+FD_DEV void sha256_load32(uint32_t (&x)[8], const uint8_t* p) {
+  const uintptr_t a = reinterpret_cast<uintptr_t>(p);
+  const uint32_t* q = reinterpret_cast<const uint32_t*>(a & ~(uintptr_t)3);
+  const uint32_t shift = (uint32_t)(a & 3);
+  uint32_t d[9];
+#pragma unroll
+  for (int i = 0; i < 8; i++) d[i] = q[i];
+  d[8] = shift ? q[8] : 0u;
+  const uint32_t sel = 0x00010203u + shift * 0x01010101u;
+#pragma unroll
+  for (int i = 0; i < 8; i++) x[i] = __builtin_amdgcn_perm(d[i + 1], d[i], sel);
+}

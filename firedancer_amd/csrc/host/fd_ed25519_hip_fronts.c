@@ -1,8 +1,8 @@
 /* fd_ed25519_hip_fronts.c -- the fronts before the verify phases
-   (include/fd_ed25519_hip.h Parts 2b-2h): stage kernel, verify_common,
+   (include/fd_ed25519_hip.h Parts 2b-2i): stage kernel, verify_common,
    finish kernel in a *_dev; pack, upload, *_dev, download, synchronise in a
    *_host ("The shape of a front"); and the rules the stage
-   kernels run, on the host (*_count, *_plan, *_root, fec_parity, fec_recover).  Part of the engine:
+   kernels run, on the host (*_count, *_plan, *_root, fec_parity, fec_recover, poh, poh_prepare).  Part of the engine:
    the *_host wrappers stage in its pinned buffers
    (fd_ed25519_hip_engine_fields.h). */
 
@@ -16,8 +16,10 @@
 #include "../fd_crds_core.h"
 #include "../fd_fec_core.h"
 #include "../fd_reedsol_core.h"
+#include "../fd_poh_core.h"
 #include "../fd_front_work.h"
 
+#include <stdlib.h>
 #include <string.h>
 
 /* What an entry point does before any work.  Returns 1 to go on (the device
@@ -880,5 +882,257 @@ fd_ed25519_hip_fec_recover_host( fd_ed25519_hip_engine_t * e, unsigned long n, u
     k0 = k1;
   }
   return FD_ED25519_HIP_OK;
+}
+
+/* ---- a block's proof-of-history hash chain (include/fd_ed25519_hip.h Part 2i) -- */
+
+_Static_assert( FD_ED25519_HIP_POH_ERR_PARSE==FD_POH_CORE_ERR_PARSE && FD_ED25519_HIP_POH_UNSUPPORTED==FD_POH_CORE_UNSUPPORTED &&
+                FD_ED25519_HIP_POH_ERR_HASH==FD_POH_CORE_ERR_HASH &&
+                FD_ED25519_HIP_POH_HASH_CNT_CEIL==FD_POH_CORE_HASH_CNT_CEIL, "public and core PoH constants differ" );
+
+/* the walk and the rules the kernels run, on the host (no GPU) */
+int
+fd_ed25519_hip_poh_prepare_count( unsigned char const * block, unsigned long block_sz, unsigned long * n,
+                                  unsigned long * n_sig ) {
+  unsigned long mb = 0UL, sg = 0UL;
+  if( !n || !n_sig || ( !block && block_sz ) ) return FD_ED25519_HIP_ERR_INVAL;
+  int code = fd_poh_core_walk( block, block_sz, 0UL, 0UL, NULL, NULL, NULL, 0UL, NULL, 0UL, &mb, &sg );
+  *n = mb; *n_sig = sg;
+  return code;
+}
+
+int
+fd_ed25519_hip_poh_prepare( unsigned char const * block, unsigned long block_sz, unsigned long first_in_off, unsigned long n,
+                            unsigned long n_sig, unsigned long * hdr_off, unsigned long * in_off, unsigned int * sig_first,
+                            unsigned long * sig_off ) {
+  unsigned long mb, sg;
+  if( !sig_first || ( n && ( !hdr_off || !in_off ) ) || ( n_sig && !sig_off ) || ( !block && block_sz ) )
+    return FD_ED25519_HIP_ERR_INVAL;
+  int code = fd_poh_core_walk( block, block_sz, 0UL, 0UL, NULL, NULL, NULL, 0UL, NULL, 0UL, &mb, &sg );
+  if( code ) return code;
+  if( mb>n || sg>n_sig ) return FD_ED25519_HIP_ERR_INVAL;
+  unsigned long spare_off = 0UL;   /* n == 0: the walk writes sig_first[ 0 ] alone */
+  return fd_poh_core_walk( block, block_sz, 0UL, first_in_off, hdr_off ? hdr_off : &spare_off, in_off, sig_first, n, sig_off,
+                           n_sig, &mb, &sg );
+}
+
+int
+fd_ed25519_hip_poh( unsigned char const * buf, unsigned long buf_sz, unsigned long n, unsigned long const * hdr_off,
+                    unsigned long const * in_off, unsigned int const * sig_first, unsigned long n_sig,
+                    unsigned long const * sig_off, unsigned long hash_cnt_max, signed char * out, unsigned char * out_hash ) {
+  if( hash_cnt_max>FD_ED25519_HIP_POH_HASH_CNT_CEIL ) return FD_ED25519_HIP_ERR_INVAL;
+  if( !n ) return FD_ED25519_HIP_OK;
+  if( !hdr_off || !in_off || !sig_first || !out || ( n_sig && !sig_off ) || ( !buf && buf_sz ) ) return FD_ED25519_HIP_ERR_INVAL;
+  for( unsigned long i=0UL; i<n; i++ )
+    out[ i ] = (signed char)fd_poh_core_verify( buf, buf_sz, hdr_off[ i ], in_off[ i ], sig_first[ i ], sig_first[ i+1UL ], n_sig,
+                                                sig_off, hash_cnt_max, out_hash ? out_hash + 32UL*i : NULL );
+  return FD_ED25519_HIP_OK;
+}
+
+int
+fd_ed25519_hip_poh_dev( fd_ed25519_hip_engine_t * e, unsigned long n, unsigned char const * buf, unsigned long buf_sz,
+                        unsigned long const * hdr_off, unsigned long const * in_off, unsigned int const * sig_first,
+                        unsigned long n_sig, unsigned long const * sig_off, unsigned long hash_cnt_max, signed char * out,
+                        unsigned char * out_hash, void * work, void * stream ) {
+  if( hash_cnt_max>FD_ED25519_HIP_POH_HASH_CNT_CEIL ) return FD_ED25519_HIP_ERR_INVAL;   /* of an empty batch too */
+  hipStream_t st;
+  int err = front_begin( e, n, buf && hdr_off && in_off && sig_first && out && work && ( !n_sig || sig_off ) &&
+                               n<=INT32_MAX && n_sig<=UINT32_MAX,
+                         (uintptr_t)work | (uintptr_t)out_hash, "poh work/out_hash", stream, &st );
+  if( err<=0 ) return err;
+  front_work_poh_t w;
+  if( (err = front_work_fits( front_work_poh( work, n, n_sig, &w ), FD_ED25519_HIP_POH_WORK_BYTES( n, n_sig ), "poh" )) ) return err;
+  fd_ed25519_poh_params_t p = { 0 };
+  p.buf = buf; p.buf_sz = buf_sz; p.hdr_off = (uint64_t const *)hdr_off; p.in_off = (uint64_t const *)in_off;
+  p.sig_first = sig_first; p.sig_off = (uint64_t const *)sig_off; p.n = n; p.n_sig = n_sig; p.hash_cnt_max = hash_cnt_max;
+  p.leaves = w.leaves; p.roots = w.roots; p.pre = w.pre; p.out = (int8_t *)out; p.out_hash = out_hash;
+  if( n_sig ) {   /* without signatures no microblock has a tree, and the chain reads neither roots nor pre */
+    HIPCHK( (hipError_t)fd_ed25519_hip_launch_poh_leaf( &p, st ), "poh_leaf launch" );
+    HIPCHK( (hipError_t)fd_ed25519_hip_launch_poh_tree( &p, st ), "poh_tree launch" );
+  }
+  HIPCHK( (hipError_t)fd_ed25519_hip_launch_poh_chain( &p, st ), "poh_chain launch" );
+  return FD_ED25519_HIP_OK;
+}
+
+/* signatures per pass of poh_host: 16 MiB of them (a microblock of more travels alone) */
+#define POH_HOST_SIGS (1UL<<18)
+/* an in_off of poh_host_impl with this bit set is an offset into `extra`
+   (poh_blocks_host's in_hash array), not into buf */
+#define POH_IN_EXTRA  (1UL<<63)
+
+typedef struct { uint64_t k; uint32_t idx; } poh_order_t;
+
+static int
+poh_order_cmp( void const * a, void const * b ) {
+  poh_order_t const * x = (poh_order_t const *)a, * y = (poh_order_t const *)b;
+  if( x->k!=y->k ) return x->k>y->k ? -1 : 1;   /* descending k */
+  return x->idx<y->idx ? -1 : x->idx>y->idx;
+}
+
+/* Judge on the host, order by descending k, then pass by pass: a
+   microblock travels as its header (48), its in state (32) and its
+   signatures (64 each), back to back in the item staging.  in: hdr_off u64
+   [m], in_off u64 [m], sig_off u64 [ns], sig_first u32 [m+1]; out: states
+   [m][32], codes [m]. */
+static int
+poh_host_impl( fd_ed25519_hip_engine_t * e, hipStream_t st, unsigned long n, unsigned char const * buf, unsigned long buf_sz,
+               unsigned long const * hdr_off, unsigned long const * in_off, unsigned int const * sig_first, unsigned long n_sig,
+               unsigned long const * sig_off, unsigned char const * extra, unsigned long hash_cnt_max, signed char * out,
+               unsigned char * out_hash ) {
+  poh_order_t * ord = (poh_order_t *)malloc( n*sizeof(poh_order_t) );
+  if( !ord ) { fd_ed25519_hip_private_set_errorf( "malloc failed" ); return FD_ED25519_HIP_ERR_NOMEM; }
+  uint64_t go = 0UL;
+  for( uint64_t i=0UL; i<n; i++ ) {
+    unsigned long k;
+    int mixin, in_extra = extra && ( in_off[ i ] & POH_IN_EXTRA );
+    /* an in state in `extra` is the caller's own: judged as if it stood at the buffer's start */
+    int code = fd_poh_core_judge( buf, buf_sz, hdr_off[ i ], in_extra ? 0UL : in_off[ i ], sig_first[ i ], sig_first[ i+1UL ],
+                                  n_sig, hash_cnt_max, &k, &mixin );
+    if( code!=FD_POH_CORE_ERR_PARSE )
+      for( uint64_t j=sig_first[ i ]; j<sig_first[ i+1UL ]; j++ )
+        if( !fd_poh_core_inside( sig_off[ j ], 64UL, buf_sz ) ) { code = FD_POH_CORE_ERR_PARSE; break; }
+    if( code==FD_POH_CORE_ERR_PARSE ) {
+      out[ i ] = (signed char)code;
+      if( out_hash ) memset( out_hash + 32UL*i, 0, 32UL );
+      continue;
+    }
+    ord[ go ].k = code ? 0UL : k;   /* an unsupported one travels and is not hashed */
+    ord[ go ].idx = (uint32_t)i;
+    go++;
+  }
+  qsort( ord, go, sizeof(poh_order_t), poh_order_cmp );
+  int err = FD_ED25519_HIP_OK;
+  for( uint64_t a=0UL; a<go && !err; ) {
+    uint64_t b = a, ns = 0UL;
+    for( ; b<go && b-a<FRONT_HOST_CHUNK; b++ ) {
+      uint64_t cnt = (uint64_t)sig_first[ ord[ b ].idx+1UL ] - sig_first[ ord[ b ].idx ];
+      if( b>a && ns+cnt>POH_HOST_SIGS ) break;
+      ns += cnt;
+    }
+    uint64_t m = b-a, bytes = 80UL*m + 64UL*ns;
+    uint64_t in_at = 8UL*m, so_at = 16UL*m, first_at = so_at + 8UL*ns, in_bytes = first_at + 4UL*( m+1UL );
+    if( (err = front_room( e, bytes, in_bytes, 33UL*m )) ) break;
+    if( (err = grow_dev( &e->d_fr_work, &e->fr_work_cap, FD_ED25519_HIP_POH_WORK_BYTES( m, ns ) )) ) break;
+    uint64_t * h_hdr   = (uint64_t *)e->h_fr_in;
+    uint64_t * h_in    = (uint64_t *)( e->h_fr_in + in_at );
+    uint64_t * h_so    = (uint64_t *)( e->h_fr_in + so_at );
+    uint32_t * h_first = (uint32_t *)( e->h_fr_in + first_at );
+    uint64_t pos = 0UL, s = 0UL;
+    for( uint64_t q=0UL; q<m; q++ ) {
+      uint64_t i = ord[ a+q ].idx;
+      int in_extra = extra && ( in_off[ i ] & POH_IN_EXTRA );
+      memcpy( e->h_msgs + pos, buf + hdr_off[ i ], 48UL );
+      memcpy( e->h_msgs + pos + 48UL, in_extra ? extra + ( in_off[ i ] & ~POH_IN_EXTRA ) : buf + in_off[ i ], 32UL );
+      h_hdr[ q ] = pos; h_in[ q ] = pos + 48UL; h_first[ q ] = (uint32_t)s;
+      pos += 80UL;
+      for( uint64_t j=sig_first[ i ]; j<sig_first[ i+1UL ]; j++, s++, pos+=64UL ) {
+        memcpy( e->h_msgs + pos, buf + sig_off[ j ], 64UL );
+        h_so[ s ] = pos;
+      }
+    }
+    h_first[ m ] = (uint32_t)s;
+    if( (err = front_upload( e, bytes, in_bytes, st )) ) break;
+    err = fd_ed25519_hip_poh_dev( e, m, e->d_msgs, bytes, (unsigned long const *)e->d_fr_in,
+                                  (unsigned long const *)( e->d_fr_in + in_at ), (unsigned int const *)( e->d_fr_in + first_at ),
+                                  ns, (unsigned long const *)( e->d_fr_in + so_at ), hash_cnt_max,
+                                  (signed char *)( e->d_fr_out + 32UL*m ), e->d_fr_out, e->d_fr_work, st );
+    if( err ) break;
+    if( (err = front_download( e, 33UL*m, st )) ) break;
+    for( uint64_t q=0UL; q<m; q++ ) {
+      uint64_t i = ord[ a+q ].idx;
+      out[ i ] = (signed char)e->h_fr_out[ 32UL*m + q ];
+      if( out_hash ) memcpy( out_hash + 32UL*i, e->h_fr_out + 32UL*q, 32UL );
+    }
+    a = b;
+  }
+  free( ord );
+  return err;
+}
+
+int
+fd_ed25519_hip_poh_host( fd_ed25519_hip_engine_t * e, unsigned long n, unsigned char const * buf, unsigned long buf_sz,
+                         unsigned long const * hdr_off, unsigned long const * in_off, unsigned int const * sig_first,
+                         unsigned long n_sig, unsigned long const * sig_off, unsigned long hash_cnt_max, signed char * out,
+                         unsigned char * out_hash ) {
+  if( hash_cnt_max>FD_ED25519_HIP_POH_HASH_CNT_CEIL ) return FD_ED25519_HIP_ERR_INVAL;
+  hipStream_t st;
+  int err = front_begin( e, n, buf && hdr_off && in_off && sig_first && out && ( !n_sig || sig_off ) && n<=INT32_MAX &&
+                               n_sig<=UINT32_MAX, 0UL, NULL, NULL, &st );
+  if( err<=0 ) return err;
+  return poh_host_impl( e, st, n, buf, buf_sz, hdr_off, in_off, sig_first, n_sig, sig_off, NULL, hash_cnt_max, out, out_hash );
+}
+
+int
+fd_ed25519_hip_poh_blocks_host( fd_ed25519_hip_engine_t * e, unsigned long nb, unsigned char const * blocks,
+                                unsigned long const * block_off, unsigned long const * block_sz, unsigned char const * in_hash,
+                                unsigned long hash_cnt_max, signed char * block_out, unsigned int * first_bad,
+                                unsigned char * out_hash ) {
+  if( hash_cnt_max>FD_ED25519_HIP_POH_HASH_CNT_CEIL ) return FD_ED25519_HIP_ERR_INVAL;
+  hipStream_t st;
+  int err = front_begin( e, nb, blocks && block_off && block_sz && in_hash && block_out && first_bad && out_hash, 0UL, NULL,
+                         NULL, &st );
+  if( err<=0 ) return err;
+  err = FD_ED25519_HIP_OK;
+  /* the walk, twice: the counts, then the arrays.  mb_at[ b ]: block b's first microblock; a block that did not walk
+     has none */
+  uint64_t * mb_at = (uint64_t *)malloc( ( nb+1UL )*sizeof(uint64_t) );
+  if( !mb_at ) { fd_ed25519_hip_private_set_errorf( "malloc failed" ); return FD_ED25519_HIP_ERR_NOMEM; }
+  uint64_t n = 0UL, n_sig = 0UL, end = 0UL;
+  for( uint64_t b=0UL; b<nb; b++ ) {
+    unsigned long mb = 0UL, sg = 0UL;
+    int code = fd_poh_core_walk( blocks + block_off[ b ], block_sz[ b ], 0UL, 0UL, NULL, NULL, NULL, 0UL, NULL, 0UL, &mb, &sg );
+    if( code || !mb ) { mb = 0UL; sg = 0UL; }
+    mb_at[ b ] = n;
+    n += mb; n_sig += sg;
+    if( mb && block_off[ b ]+block_sz[ b ]>end ) end = block_off[ b ]+block_sz[ b ];
+  }
+  mb_at[ nb ] = n;
+  if( n>INT32_MAX || n_sig>UINT32_MAX ) { free( mb_at ); return FD_ED25519_HIP_ERR_INVAL; }
+  unsigned long * hdr_off   = (unsigned long *)malloc( ( n ? n : 1UL )*sizeof(unsigned long) );
+  unsigned long * in_off    = (unsigned long *)malloc( ( n ? n : 1UL )*sizeof(unsigned long) );
+  unsigned int *  sig_first = (unsigned int *) malloc( ( n+1UL )*sizeof(unsigned int) );
+  unsigned long * sig_off   = (unsigned long *)malloc( ( n_sig ? n_sig : 1UL )*sizeof(unsigned long) );
+  signed char *   out       = (signed char *)  malloc( n ? n : 1UL );
+  if( !hdr_off || !in_off || !sig_first || !sig_off || !out ) {
+    fd_ed25519_hip_private_set_errorf( "malloc failed" );
+    err = FD_ED25519_HIP_ERR_NOMEM;
+  }
+  uint64_t sg_at = 0UL;
+  for( uint64_t b=0UL; b<nb && !err; b++ ) {
+    uint64_t m0 = mb_at[ b ], mb_cnt = mb_at[ b+1UL ]-m0;
+    if( !mb_cnt ) continue;
+    unsigned long mb, sg;
+    /* sig_first comes back relative to the block's first signature; the block's last element is the next one's first */
+    fd_poh_core_walk( blocks + block_off[ b ], block_sz[ b ], block_off[ b ], POH_IN_EXTRA | ( 32UL*b ), hdr_off + m0, in_off + m0,
+                      sig_first + m0, mb_cnt, sig_off + sg_at, n_sig-sg_at, &mb, &sg );
+    for( uint64_t i=m0; i<m0+mb_cnt; i++ ) sig_first[ i ] += (unsigned int)sg_at;
+    sg_at += sg;
+  }
+  if( !err ) {
+    sig_first[ n ] = (unsigned int)n_sig;
+    if( n ) err = poh_host_impl( e, st, n, blocks, end, hdr_off, in_off, sig_first, n_sig, sig_off, in_hash, hash_cnt_max, out,
+                                 NULL );
+  }
+  /* fd_runtime_block_verify_tpool's reduction */
+  for( uint64_t b=0UL; b<nb && !err; b++ ) {
+    uint64_t m0 = mb_at[ b ], m1 = mb_at[ b+1UL ];
+    first_bad[ b ] = 0xFFFFFFFFU;
+    if( m0==m1 ) {
+      block_out[ b ] = FD_ED25519_HIP_POH_ERR_PARSE;
+      memset( out_hash + 32UL*b, 0, 32UL );
+      continue;
+    }
+    int any_hash = 0, any_unsup = 0;
+    for( uint64_t i=m1; i>m0; i-- )
+      if( out[ i-1UL ] ) {
+        first_bad[ b ] = (unsigned int)( i-1UL-m0 );
+        any_hash  |= out[ i-1UL ]==FD_ED25519_HIP_POH_ERR_HASH;
+        any_unsup |= out[ i-1UL ]==FD_ED25519_HIP_POH_UNSUPPORTED;
+      }
+    block_out[ b ] = (signed char)( any_hash ? FD_ED25519_HIP_POH_ERR_HASH : any_unsup ? FD_ED25519_HIP_POH_UNSUPPORTED : 0 );
+    memcpy( out_hash + 32UL*b, blocks + hdr_off[ m1-1UL ] + 8UL, 32UL );
+  }
+  free( mb_at ); free( hdr_off ); free( in_off ); free( sig_first ); free( sig_off ); free( out );
+  return err;
 }
 

@@ -255,6 +255,67 @@ def fec_recover(shreds, erased):
     return code, [buf[int(off[i]):int(off[i]) + int(sz[i])].tobytes() for i in range(cnt)]
 
 
+# a block's proof-of-history hash chain (include/fd_ed25519_hip.h Part 2i)
+POH_ERR_PARSE = -16
+POH_UNSUPPORTED = -18
+POH_ERR_HASH = -25
+POH_HASH_CNT_CEIL = 1 << 17
+_lib.fd_ed25519_hip_poh_prepare_count.argtypes = [_u8p, ctypes.c_ulong, _u8p, _u8p]
+_lib.fd_ed25519_hip_poh_prepare.argtypes = [_u8p] + [ctypes.c_ulong] * 4 + [_u8p] * 4
+_lib.fd_ed25519_hip_poh.argtypes = [_u8p, ctypes.c_ulong, ctypes.c_ulong] + [_u8p] * 3 + [ctypes.c_ulong, _u8p, ctypes.c_ulong,
+                                                                                        _u8p, _u8p]
+_lib.fd_ed25519_hip_poh_dev.argtypes = ([ctypes.c_void_p, ctypes.c_ulong, _u8p, ctypes.c_ulong] + [_u8p] * 3 +
+                                        [ctypes.c_ulong, _u8p, ctypes.c_ulong] + [_u8p] * 4)
+_lib.fd_ed25519_hip_poh_host.argtypes = ([ctypes.c_void_p, ctypes.c_ulong, _u8p, ctypes.c_ulong] + [_u8p] * 3 +
+                                         [ctypes.c_ulong, _u8p, ctypes.c_ulong] + [_u8p] * 2)
+_lib.fd_ed25519_hip_poh_blocks_host.argtypes = [ctypes.c_void_p, ctypes.c_ulong] + [_u8p] * 4 + [ctypes.c_ulong] + [_u8p] * 3
+
+
+def poh_work_bytes(n, n_sig):
+    """FD_ED25519_HIP_POH_WORK_BYTES"""
+    return 32 * int(n_sig) + 33 * int(n) + 16
+
+
+def poh_prepare(block, first_in_off=0):
+    """fd_ed25519_hip_poh_prepare_count + _prepare: the walk of one raw block
+    -> (code, hdr_off u64[n], in_off u64[n], sig_first u32[n+1], sig_off
+    u64[n_sig]), offsets relative to the block's first byte and in_off[0] =
+    first_in_off; the arrays are None when the code is not 0 (host only)."""
+    block = np.frombuffer(bytes(block), np.uint8) if len(block) else np.zeros(0, np.uint8)
+    n, n_sig = ctypes.c_ulong(0), ctypes.c_ulong(0)
+    ptr = _ptr(block) if len(block) else None
+    code = _lib.fd_ed25519_hip_poh_prepare_count(ptr, len(block), ctypes.byref(n), ctypes.byref(n_sig))
+    if code:
+        return code, None, None, None, None
+    n, n_sig = n.value, n_sig.value
+    hdr, inn = np.zeros(max(1, n), np.uint64), np.zeros(max(1, n), np.uint64)
+    first, sig = np.zeros(n + 1, np.uint32), np.zeros(max(1, n_sig), np.uint64)
+    code = _lib.fd_ed25519_hip_poh_prepare(ptr, len(block), int(first_in_off), n, n_sig, _ptr(hdr), _ptr(inn), _ptr(first),
+                                           _ptr(sig))
+    assert code == 0, code
+    return 0, hdr[:n], inn[:n], first, sig[:n_sig]
+
+
+def _poh_args(buf, hdr_off, in_off, sig_first, sig_off):
+    buf = np.frombuffer(bytes(buf), np.uint8) if not isinstance(buf, np.ndarray) else _c(buf, np.uint8)
+    hdr, inn = _c(hdr_off, np.uint64), _c(in_off, np.uint64)
+    first, sig = _c(sig_first, np.uint32), _c(sig_off, np.uint64)
+    n = len(hdr)
+    assert len(inn) == n and len(first) == n + 1
+    return buf, hdr, inn, first, sig, n
+
+
+def poh_verify(buf, hdr_off, in_off, sig_first, sig_off, hash_cnt_max=POH_HASH_CNT_CEIL):
+    """fd_ed25519_hip_poh: (int8 code per microblock, the computed states
+    uint8[n][32]) of the microblocks described by offsets into buf (host
+    only)."""
+    buf, hdr, inn, first, sig, n = _poh_args(buf, hdr_off, in_off, sig_first, sig_off)
+    out, states = np.zeros(max(1, n), np.int8), np.zeros((max(1, n), 32), np.uint8)
+    _check(_lib.fd_ed25519_hip_poh(_ptr(buf) if len(buf) else None, len(buf), n, _ptr(hdr), _ptr(inn), _ptr(first), len(sig),
+                                   _ptr(sig) if len(sig) else None, int(hash_cnt_max), _ptr(out), _ptr(states)))
+    return out[:n], states[:n]
+
+
 # signed gossip and repair control packets (include/fd_ed25519_hip.h Part 2d)
 PROTO_GOSSIP = 0
 PROTO_REPAIR_SERV = 1
@@ -672,6 +733,41 @@ class Engine:
         """Device-resident fd_ed25519_hip_fec_recover_dev: device addresses (ints); async."""
         _check(_lib.fd_ed25519_hip_fec_recover_dev(self._h, int(n), d_shreds, d_off, d_sz, d_erased, int(n_set), d_set_first,
                                                    d_set_out, stream))
+
+    def poh_host(self, buf, hdr_off, in_off, sig_first, sig_off, hash_cnt_max=POH_HASH_CNT_CEIL):
+        """fd_ed25519_hip_poh_host: (int8 code per microblock, the computed
+        states uint8[n][32]) of the microblocks described by offsets into
+        buf; synchronous."""
+        buf, hdr, inn, first, sig, n = _poh_args(buf, hdr_off, in_off, sig_first, sig_off)
+        out, states = np.zeros(max(1, n), np.int8), np.zeros((max(1, n), 32), np.uint8)
+        _check(_lib.fd_ed25519_hip_poh_host(self._h, n, _ptr(buf) if len(buf) else None, len(buf), _ptr(hdr), _ptr(inn),
+                                            _ptr(first), len(sig), _ptr(sig) if len(sig) else None, int(hash_cnt_max),
+                                            _ptr(out), _ptr(states)))
+        return out[:n], states[:n]
+
+    def poh_blocks_host(self, blocks, in_hashes, hash_cnt_max=POH_HASH_CNT_CEIL):
+        """fd_ed25519_hip_poh_blocks_host: blocks is a list of raw blocks,
+        in_hashes the 32-byte hash each one's first microblock starts from ->
+        (int8 code per block, uint32 first_bad per block, the last
+        microblock's header hash uint8[nb][32]); synchronous."""
+        from .tile import pack_payloads
+        nb = len(blocks)
+        assert len(in_hashes) == nb
+        codes, bad, last = np.zeros(max(1, nb), np.int8), np.zeros(max(1, nb), np.uint32), np.zeros((max(1, nb), 32), np.uint8)
+        if nb:
+            buf, off, sz = pack_payloads([bytes(b) for b in blocks])
+            inh = np.frombuffer(b"".join(bytes(h) for h in in_hashes), np.uint8)
+            assert len(inh) == 32 * nb
+            off, sz = _c(off, np.uint64), _c(sz, np.uint64)
+            _check(_lib.fd_ed25519_hip_poh_blocks_host(self._h, nb, _ptr(buf), _ptr(off), _ptr(sz), _ptr(inh), int(hash_cnt_max),
+                                                       _ptr(codes), _ptr(bad), _ptr(last)))
+        return codes[:nb], bad[:nb], last[:nb]
+
+    def poh_dev(self, n, d_buf, buf_sz, d_hdr_off, d_in_off, d_sig_first, n_sig, d_sig_off, hash_cnt_max, d_out, d_out_hash,
+                d_work, stream=None):
+        """Device-resident fd_ed25519_hip_poh_dev: device addresses (ints); async."""
+        _check(_lib.fd_ed25519_hip_poh_dev(self._h, int(n), d_buf, int(buf_sz), d_hdr_off, d_in_off, d_sig_first, int(n_sig),
+                                           d_sig_off, int(hash_cnt_max), d_out, d_out_hash, d_work, stream))
 
     # ---- batched signing / synthetic workloads -------------------------
     def sign_dev(self, n, d_msgs, d_off, d_sz, d_privs, d_sigs, d_pubs, stream=None):

@@ -215,8 +215,9 @@ typedef struct fd_ed25519_hip_engine fd_ed25519_hip_engine_t;
    Part 2e, the CRDS values of gossip pull responses and push messages; 15:
    Part 2f, sealing a leader's FEC sets; 16: Part 2g, the Reed-Solomon
    parity of a leader's FEC sets; still 16 with Part 2h, recovering received
-   FEC sets: it only adds entry points and two codes, and nothing a consumer
-   of version 16 was built against has changed).
+   FEC sets, and Part 2i, a block's proof-of-history hash chain: they only
+   add entry points and three codes, and nothing a consumer of version 16
+   was built against has changed).
    A consumer checks
    the library it loaded against the header it was built with:
    fd_ed25519_hip_abi_check( FD_ED25519_HIP_ABI_VERSION,
@@ -1287,6 +1288,192 @@ fd_ed25519_hip_fec_recover_host( fd_ed25519_hip_engine_t * engine,
                                  unsigned long             n_set,
                                  unsigned int const *      set_first,
                                  signed char *             set_out );
+
+/* ---- Part 2i: a block's proof-of-history hash chain ---------------------- */
+
+/* What a validator does with the bytes that come out of its recovered FEC
+   sets, beside verifying the transactions' signatures: the data shreds'
+   payloads laid end to end are a block's entry batches, and every
+   microblock's proof-of-history hash is checked (fd_runtime_block_verify /
+   fd_runtime_poh_verify_wide_task, src/flamenco/runtime/fd_runtime.c:
+   2007-2106).
+
+   A microblock is given by offsets into one byte buffer buf[0, buf_sz): its
+   48-byte header at hdr_off (hash_cnt u64 at 0x00, hash[32] at 0x08, txn_cnt
+   u64 at 0x28, little-endian), the 32-byte state it starts from at in_off (a
+   chained microblock's is its predecessor's hdr_off + 8; a block's first is
+   wherever the caller put the parent's hash), and the 64-byte signatures of
+   its transactions in transaction order at sig_off[sig_first[i] ..
+   sig_first[i+1]).  Every field may stand at any byte address.
+
+     txn_cnt == 0: k = hash_cnt, no mixin;
+     txn_cnt  > 0: k = hash_cnt ? hash_cnt - 1 : 0, then a mixin (so hash_cnt
+                   0 and 1 give the same result, as in the reference);
+     state = in, k times state = SHA256( state ) (fd_poh_append), then the
+     mixin state = SHA256( state || root ) (fd_poh_mixin), root the
+     fd_wbmtree32 root over the signatures: leaf SHA256( 0x00 || sig ), node
+     SHA256( 0x01 || left || right ), a layer of odd size duplicates its last
+     node, a single leaf is the root (fd_bmtree_commit with 32-byte nodes and
+     the 1-byte prefix gives the same root);
+     0 if state equals the header's hash, else POH_ERR_HASH.
+
+   POH_ERR_PARSE for a descriptor fd_runtime_block_prepare cannot produce: a
+   signature range that runs backwards or leaves [0, n_sig), txn_cnt > 0 with
+   no signatures, txn_cnt == 0 with some, an offset whose field leaves the
+   buffer.  POH_UNSUPPORTED if k > hash_cnt_max.  Parse comes before
+   unsupported, unsupported before hash.
+
+   The bound is the one deliberate difference from the reference: hash_cnt is
+   64 attacker-chosen bits and the reference would simply hash for years
+   (its TODO about hashes_per_slot is the same gap).  Every entry point takes
+   hash_cnt_max, at most FD_ED25519_HIP_POH_HASH_CNT_CEIL (above it the call
+   is ERR_INVAL); a microblock over it is not hashed at all, and the kernel's
+   loop bound is the minimum of k and hash_cnt_max besides, so no descriptor
+   makes a launch longer than the ceiling allows.  fd_ed25519_hip_poh is a
+   caller's CPU path for an UNSUPPORTED microblock it believes.
+
+   One lane runs one chain: a lone microblock is far slower here than on a
+   CPU core with SHA extensions.  The calls pay where many microblocks are
+   verified together -- ledger replay, catch-up, repair of many slots
+   (with the measurement).
+
+   Out of scope: a deshredder, a combined PoH + signature-verify call, the
+   tick-count and hashes_per_slot consensus checks, and a sub-wave tree for
+   tiny microblocks. */
+#define FD_ED25519_HIP_POH_ERR_PARSE     (-16)   /* a descriptor the block walk cannot produce */
+#define FD_ED25519_HIP_POH_UNSUPPORTED   (-18)   /* more hashes than hash_cnt_max */
+#define FD_ED25519_HIP_POH_ERR_HASH      (-25)   /* the computed state is not the header's hash */
+#define FD_ED25519_HIP_POH_HASH_CNT_CEIL (1UL<<17)   /* twice a mainnet tick (62,500) */
+
+/* The block walk, host only (no GPU): fd_runtime_block_prepare
+   (fd_runtime.c:349-580) over one raw block -- batches until the buffer
+   ends, each a u64 microblock_cnt and that many microblocks, each a header
+   and txn_cnt transactions (fd_txn_parse_core's payload-size form on at
+   most 1,232 of the bytes that remain).  Counts are believed only as far as
+   bytes remain.  POH_ERR_PARSE: junk at the end, a short header, a failed
+   transaction parse, and a batch with microblock_cnt == 0 (the reference's
+   collect step reads microblock -1 of such a batch: undefined there,
+   refused here).
+
+   prepare_count returns 0 with the block's microblocks in *n and signatures
+   in *n_sig, else POH_ERR_PARSE (both 0).  prepare fills hdr_off[n],
+   in_off[n] (first_in_off for microblock 0, else the predecessor's hdr_off +
+   8, across batch boundaries too), sig_first[n+1] and sig_off[n_sig], every
+   offset relative to the block's first byte; n and n_sig are the capacities,
+   and ERR_INVAL comes back if the block needs more of either. */
+int
+fd_ed25519_hip_poh_prepare_count( unsigned char const * block,
+                                  unsigned long         block_sz,
+                                  unsigned long *       n,
+                                  unsigned long *       n_sig );
+
+int
+fd_ed25519_hip_poh_prepare( unsigned char const * block,
+                            unsigned long         block_sz,
+                            unsigned long         first_in_off,
+                            unsigned long         n,
+                            unsigned long         n_sig,
+                            unsigned long *       hdr_off,
+                            unsigned long *       in_off,
+                            unsigned int *        sig_first,
+                            unsigned long *       sig_off );
+
+/* n microblocks, host only (no GPU), from the same rules as the device's
+   kernels and the portable SHA-256 of fd_ed25519_hip_shred_root.  out[i]
+   receives microblock i's code; out_hash (optional) its computed state at
+   out_hash + 32 i, zeros for POH_ERR_PARSE and POH_UNSUPPORTED.  Returns
+   ERR_INVAL for hash_cnt_max above the ceiling or a missing array. */
+int
+fd_ed25519_hip_poh( unsigned char const * buf,
+                    unsigned long         buf_sz,
+                    unsigned long         n,
+                    unsigned long const * hdr_off,
+                    unsigned long const * in_off,
+                    unsigned int const *  sig_first,
+                    unsigned long         n_sig,
+                    unsigned long const * sig_off,
+                    unsigned long         hash_cnt_max,
+                    signed char *         out,
+                    unsigned char *       out_hash );
+
+/* Device workspace of poh_dev: a leaf hash per signature (32), which the
+   tree reduces in place; per microblock its root (32) and one flag. */
+#define FD_ED25519_HIP_POH_WORK_BYTES( n, n_sig ) \
+  ( 32UL*(unsigned long)(n_sig) + 33UL*(unsigned long)(n) + 16UL )
+
+/* Device-resident batch: every pointer but the engine is a device pointer.
+   buf may start at any byte of a device allocation and must stay readable
+   at least 16 bytes past buf + buf_sz; no alignment is asked of any field
+   in it.  sig_first has n+1 elements; a sig_first that is not
+   non-decreasing is survived (a range that runs backwards is
+   POH_ERR_PARSE; microblocks whose ranges of more than 128 signatures
+   overlap get an unspecified one of 0 and POH_ERR_HASH) and nothing is read
+   or written outside the arrays.  out[i] receives the code; out_hash
+   (optional, 16-byte aligned) the state as for fd_ed25519_hip_poh.  work:
+   16-byte aligned, FD_ED25519_HIP_POH_WORK_BYTES( n, n_sig ) bytes.
+   n < 2^31, n_sig < 2^32.
+
+   Asynchronous on `stream` (NULL: the engine's): three launches (a lane per
+   signature for the leaves, a wave per microblock for its tree, a lane per
+   microblock for the chain; the chain alone when n_sig is 0); it allocates
+   nothing and does not synchronise.  n==0 is a no-op. */
+int
+fd_ed25519_hip_poh_dev( fd_ed25519_hip_engine_t * engine,
+                        unsigned long             n,
+                        unsigned char const *     buf,
+                        unsigned long             buf_sz,
+                        unsigned long const *     hdr_off,
+                        unsigned long const *     in_off,
+                        unsigned int const *      sig_first,
+                        unsigned long             n_sig,
+                        unsigned long const *     sig_off,
+                        unsigned long             hash_cnt_max,
+                        signed char *             out,
+                        unsigned char *           out_hash,
+                        void *                    work,
+                        void *                    stream );
+
+/* Host-buffer batch, synchronous: orders the microblocks by descending k so
+   that the lanes of a wave run alike, packs each one's header, in state and
+   signatures into pinned staging memory (in passes, so any n fits), copies,
+   runs poh_dev and returns out[0..n) and out_hash (optional, n x 32) in the
+   caller's order.  A microblock with POH_ERR_PARSE is judged on the host
+   and does not travel.  No alignment is asked of any argument. */
+int
+fd_ed25519_hip_poh_host( fd_ed25519_hip_engine_t * engine,
+                         unsigned long             n,
+                         unsigned char const *     buf,
+                         unsigned long             buf_sz,
+                         unsigned long const *     hdr_off,
+                         unsigned long const *     in_off,
+                         unsigned int const *      sig_first,
+                         unsigned long             n_sig,
+                         unsigned long const *     sig_off,
+                         unsigned long             hash_cnt_max,
+                         signed char *             out,
+                         unsigned char *           out_hash );
+
+/* nb raw blocks, block b the bytes blocks[block_off[b] .. block_off[b] +
+   block_sz[b]) and in_hash + 32 b the hash its first microblock starts from:
+   the walk, poh_host over the microblocks of every block that walked, and
+   fd_runtime_block_verify_tpool's reduction.  block_out[b]: POH_ERR_PARSE if
+   the walk failed or found no microblock (nothing of the block is verified);
+   else POH_ERR_HASH if any microblock mismatched; else POH_UNSUPPORTED if any
+   was over hash_cnt_max; else 0.  first_bad[b]: the block's first
+   microblock with a nonzero code, 0xFFFFFFFF if none.  out_hash + 32 b: the
+   last microblock's header hash (fd_runtime.c:2097), zeros for a block that
+   did not walk.  Synchronous. */
+int
+fd_ed25519_hip_poh_blocks_host( fd_ed25519_hip_engine_t * engine,
+                                unsigned long             nb,
+                                unsigned char const *     blocks,
+                                unsigned long const *     block_off,
+                                unsigned long const *     block_sz,
+                                unsigned char const *     in_hash,
+                                unsigned long             hash_cnt_max,
+                                signed char *             block_out,
+                                unsigned int *            first_bad,
+                                unsigned char *           out_hash );
 
 /* ---- Part 3: batched signing and the synthetic workload generator ------ */
 
