@@ -41,17 +41,13 @@
 
 #define FD_SHRED_FN __device__ static inline
 #include "fd_reedsol_core.h"
+#include "fd_reedsol_dev.h"
 
 #define FD_RC_BLOCK   256   /* 255 columns at depth 6 (32+32), 250 at depth 7 */
 #define FD_RC_ROWS    32    /* targets a pass: their accumulators live in registers */
 #define FD_RC_STRIDE  68    /* a row of coefficients in LDS: 67 padded to whole dwords */
 #define FD_RC_ROW_MAX 160   /* at most 133 targets; a pass may start at any row and runs to a multiple of 8 behind it */
 #define FD_RC_HDR_COLS 7    /* the columns that hold a data shred's bytes [0x40, 0x59) */
-
-/* the four products c x of x's bytes from c's 20 table bytes */
-__device__ __forceinline__ uint32_t rc_mul(const uint4 t, const uint32_t t2, const uint32_t s0, const uint32_t s1, const uint32_t s2) {
-  return __builtin_amdgcn_perm(t.y, t.x, s0) ^ __builtin_amdgcn_perm(t.w, t.z, s1) ^ __builtin_amdgcn_perm(0u, t2, s2);
-}
 
 struct rc_lds_t {
   uint4    mul[FD_REEDSOL_CORE_MUL_BYTES / 16];          /* [256][2]: T0 T1 | T2 pad */
@@ -91,7 +87,7 @@ __device__ __forceinline__ uint32_t rc_rows(const fd_ed25519_fec_recover_params_
         for (int u = 0; u < 4; u++) {
           /* a column of the last region bytes may reach one byte into the proof: inside the shred */
           const uint32_t x = i0 + u < d ? load4_any(p.shreds + s.src[i0 + u] + 4u * col) : 0u;
-          s0[u] = x & 0x07070707u; s1[u] = (x >> 3) & 0x07070707u; s2[u] = (x >> 6) & 0x03030303u;
+          fd_reedsol_sel(x, s0[u], s1[u], s2[u]);
         }
 #pragma unroll
         for (int g = 0; g < FD_RC_ROWS; g += 8) {
@@ -102,7 +98,7 @@ __device__ __forceinline__ uint32_t rc_rows(const fd_ed25519_fec_recover_params_
 #pragma unroll
               for (int u = 0; u < 4; u++) {
                 const uint32_t c = (c4 >> (8 * u)) & 0xffu;
-                acc[r] ^= rc_mul(s.mul[2 * c], s.mul[2 * c + 1].x, s0[u], s1[u], s2[u]);
+                acc[r] ^= fd_reedsol_mul(s.mul[2 * c], s.mul[2 * c + 1].x, s0[u], s1[u], s2[u]);
               }
             }
           }
@@ -237,7 +233,7 @@ fd_ed25519_fec_recover_kernel(fd_ed25519_fec_recover_params_t p) {
 #pragma unroll
         for (int u = 0; u < 8; u++) {
           const uint32_t c = coef8[r * FD_RC_STRIDE + i0 + u];   /* zero beyond d */
-          acc ^= rc_mul(s.mul[2 * c], s.mul[2 * c + 1].x, x[u] & 0x07070707u, (x[u] >> 3) & 0x07070707u, (x[u] >> 6) & 0x03030303u);
+          acc ^= fd_reedsol_mul(s.mul[2 * c], s.mul[2 * c + 1].x, x[u] & 0x07070707u, (x[u] >> 3) & 0x07070707u, (x[u] >> 6) & 0x03030303u);
         }
       }
       s.hdr[s.tgt[r] * FD_RC_HDR_COLS + col] = acc;

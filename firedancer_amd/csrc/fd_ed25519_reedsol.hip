@@ -33,16 +33,12 @@
 
 #define FD_SHRED_FN __device__ static inline
 #include "fd_reedsol_core.h"
+#include "fd_reedsol_dev.h"
 
 #define FD_RS_BLOCK  256   /* 255 columns at depth 6 (32+32), 250 at depth 7 */
 #define FD_RS_ROWS   32    /* parity rows a pass: their accumulators live in registers */
 #define FD_RS_STRIDE 68    /* a row of coefficients in LDS: 67 padded to whole dwords */
 #define FD_RS_ROW_MAX ( ( ( FD_REEDSOL_CORE_MAX + FD_RS_ROWS - 1 ) / FD_RS_ROWS ) * FD_RS_ROWS )
-
-/* the four products c x of x's bytes from c's 20 table bytes */
-__device__ __forceinline__ uint32_t rs_mul(const uint4 t, const uint32_t t2, const uint32_t s0, const uint32_t s1, const uint32_t s2) {
-  return __builtin_amdgcn_perm(t.y, t.x, s0) ^ __builtin_amdgcn_perm(t.w, t.z, s1) ^ __builtin_amdgcn_perm(0u, t2, s2);
-}
 
 __global__ void __launch_bounds__(FD_RS_BLOCK)
 fd_ed25519_fec_parity_kernel(fd_ed25519_fec_parity_params_t p) {
@@ -102,7 +98,7 @@ fd_ed25519_fec_parity_kernel(fd_ed25519_fec_parity_params_t p) {
         for (int u = 0; u < 4; u++) {
           /* a column of the last data shred may reach one byte into its proof: inside the shred */
           const uint32_t x = i0 + u < d ? load4_any(p.shreds + p.shred_off[first + i0 + u] + FD_REEDSOL_CORE_DATA_AT + 4u * col) : 0u;
-          s0[u] = x & 0x07070707u; s1[u] = (x >> 3) & 0x07070707u; s2[u] = (x >> 6) & 0x03030303u;
+          fd_reedsol_sel(x, s0[u], s1[u], s2[u]);
         }
 #pragma unroll
         for (int g = 0; g < FD_RS_ROWS; g += 8) {
@@ -113,7 +109,7 @@ fd_ed25519_fec_parity_kernel(fd_ed25519_fec_parity_params_t p) {
 #pragma unroll
               for (int u = 0; u < 4; u++) {
                 const uint32_t c = (c4 >> (8 * u)) & 0xffu;
-                acc[r] ^= rs_mul(s_mul[2 * c], s_mul[2 * c + 1].x, s0[u], s1[u], s2[u]);
+                acc[r] ^= fd_reedsol_mul(s_mul[2 * c], s_mul[2 * c + 1].x, s0[u], s1[u], s2[u]);
               }
             }
           }

@@ -7,6 +7,8 @@ import functools
 import random
 import struct
 
+import numpy as np
+
 import fec_model as model
 from conftest import load_golden
 from shred_util import fixture
@@ -201,3 +203,87 @@ def mutated_sets(count=2000, seed=71):
                 s.insert(j, s[j])
         out.append(tuple(s))
     return tuple(out)
+
+
+# ---- the device-resident run the GPU test modules share (fd_ed25519_hip_fec_seal_dev) ----
+
+def expect(oracle, sets, privs):
+    """the model's (code, shreds, root, signature) per set"""
+    return [model.seal(oracle, s, None if privs is None else privs[k]) for k, s in enumerate(sets)]
+
+
+def check_outputs(want, codes, roots, sigs):
+    assert codes.tolist() == [w[0] for w in want]
+    for k, (code, _, root, sig) in enumerate(want):
+        assert roots[k].tobytes() == (root if code == 0 else bytes(32)), k
+        if sigs is not None:
+            assert sigs[k].tobytes() == (sig if code == 0 else bytes(64)), k
+
+
+def check_front(eng, want, pubs):
+    """every shred of a sealed set passes fd_ed25519_hip_shreds_host under its key"""
+    shreds = [s for k, w in enumerate(want) if w[0] == 0 for s in w[1]]
+    leaders = [pubs[k] for k, w in enumerate(want) if w[0] == 0 for _ in w[1]]
+    codes, _ = eng.shreds_host(shreds, leaders)
+    assert len(shreds) and not codes.any(), np.nonzero(codes)[0][:10]
+
+
+def run_dev(eng, ed, oracle, sets, privs, pubs, place, set_first=None):
+    """fd_ed25519_hip_fec_seal_dev on a device-resident buffer of guard bytes
+    in which place(i, end of the previous shred) says where shred i starts;
+    the whole buffer afterwards must be the same layout of the model's
+    shreds: guard bytes before, between and after the shreds unchanged"""
+    flat = [s for st in sets for s in st]
+    n, n_set = len(flat), len(sets)
+    if set_first is None:
+        set_first = np.cumsum([0] + [len(s) for s in sets])
+    want = expect(oracle, sets, privs)
+    flat_want = [s for w in want for s in w[1]]
+    rng = random.Random(79)
+    off, end = [], 0
+    for i, s in enumerate(flat):
+        off.append(place(i, end))
+        assert off[-1] >= end
+        end = off[-1] + len(s)
+    size = end + 64
+    guard = bytes(rng.getrandbits(8) for _ in range(size))
+    before, after = bytearray(guard), bytearray(guard)
+    for o, s, w in zip(off, flat, flat_want):
+        before[o:o + len(s)] = s
+        after[o:o + len(s)] = w
+    d_buf = eng.alloc(size).upload(np.frombuffer(bytes(before), np.uint8))
+    d_off = eng.alloc(8 * n + 8).upload(np.array(off + [0], np.uint64))
+    d_sz = eng.alloc(4 * n + 4).upload(np.array([len(s) for s in flat] + [0], np.uint32))
+    d_first = eng.alloc(4 * (n_set + 1)).upload(np.array(set_first, np.uint32))
+    d_privs = eng.alloc(32 * n_set).upload(np.frombuffer(b"".join(privs), np.uint8)) if privs is not None else None
+    d_work = eng.alloc(ed.fec_work_bytes(n, n_set))
+    d_out = eng.alloc(n_set + 8).upload(np.full(n_set + 8, 0x55, np.int8))
+    d_roots = eng.alloc(32 * (n_set + 1)).upload(np.full(32 * (n_set + 1), 0x55, np.uint8))
+    d_sigs = eng.alloc(64 * (n_set + 1)).upload(np.full(64 * (n_set + 1), 0x55, np.uint8))
+    eng.fec_seal_dev(n, d_buf.ptr, d_off.ptr, d_sz.ptr, n_set, d_first.ptr, d_privs.ptr if privs is not None else None, d_work.ptr,
+                     d_out.ptr, d_roots.ptr, d_sigs.ptr if privs is not None else None)
+    eng.sync()
+    buf = d_buf.download(np.uint8, size).tobytes()
+    out = d_out.download(np.int8, n_set + 8)
+    roots = d_roots.download(np.uint8, 32 * (n_set + 1))
+    sigs = d_sigs.download(np.uint8, 64 * (n_set + 1))
+    for b in (d_buf, d_off, d_sz, d_first, d_privs, d_work, d_out, d_roots, d_sigs):
+        if b is not None:
+            b.free()
+    # nothing written past the n_set results, nor into an output that was not given
+    assert (out[n_set:] == 0x55).all() and (roots[32 * n_set:] == 0x55).all() and (sigs[64 * n_set:] == 0x55).all()
+    if privs is None:
+        assert (sigs == 0x55).all()
+    check_outputs(want, out[:n_set], roots[:32 * n_set].reshape(n_set, 32),
+                  sigs[:64 * n_set].reshape(n_set, 64) if privs is not None else None)
+    if buf != bytes(after):
+        at = next(i for i in range(size) if buf[i] != after[i])
+        which = max((i for i in range(n) if off[i] <= at), default=-1)
+        raise AssertionError(f"byte {at} of the buffer differs: shred {which} starts at {off[which] if which >= 0 else None}")
+    if privs is not None:
+        check_front(eng, want, pubs)
+    return want
+
+
+def back_to_back(i, end):
+    return end + 16 if i == 0 else end

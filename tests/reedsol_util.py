@@ -7,6 +7,8 @@ import functools
 import random
 import struct
 
+import numpy as np
+
 import fec_model
 import fec_util
 import reedsol_model as rs
@@ -111,3 +113,58 @@ def all_bad_sets():
         assert rs.parity_code(s) == want, name
         old.append((name, list(s), want))
     return old + [(name, list(s), want) for name, s, want, _ in rule_cases()]
+
+
+# ---- the device-resident run the GPU test modules share (fd_ed25519_hip_fec_parity_dev) ----
+
+def expect(sets):
+    """the model's (code, shreds) per set"""
+    return [rs.fill(list(s)) for s in sets]
+
+
+def run_dev(eng, sets, place, want=None, set_first=None):
+    """fd_ed25519_hip_fec_parity_dev on a device-resident buffer of guard
+    bytes in which place(i, end of the previous shred) says where shred i
+    starts; the whole buffer afterwards must be the same layout of the
+    model's shreds: guard bytes, headers, data shreds, signatures and proofs
+    unchanged"""
+    flat = [s for st in sets for s in st]
+    n, n_set = len(flat), len(sets)
+    if set_first is None:
+        set_first = np.cumsum([0] + [len(s) for s in sets])
+    want = expect(sets) if want is None else want
+    flat_want = [s for w in want for s in w[1]]
+    rng = random.Random(163)
+    off, end = [], 0
+    for i, s in enumerate(flat):
+        off.append(place(i, end))
+        assert off[-1] >= end
+        end = off[-1] + len(s)
+    size = end + 64
+    guard = rng.randbytes(size)
+    before, after = bytearray(guard), bytearray(guard)
+    for o, s, w in zip(off, flat, flat_want):
+        before[o:o + len(s)] = s
+        after[o:o + len(s)] = w
+    d_buf = eng.alloc(size).upload(np.frombuffer(bytes(before), np.uint8))
+    d_off = eng.alloc(8 * n + 8).upload(np.array(off + [0], np.uint64))
+    d_sz = eng.alloc(4 * n + 4).upload(np.array([len(s) for s in flat] + [0], np.uint32))
+    d_first = eng.alloc(4 * (n_set + 1)).upload(np.array(set_first, np.uint32))
+    d_out = eng.alloc(n_set + 8).upload(np.full(n_set + 8, 0x55, np.int8))
+    eng.fec_parity_dev(n, d_buf.ptr, d_off.ptr, d_sz.ptr, n_set, d_first.ptr, d_out.ptr)
+    eng.sync()
+    buf = d_buf.download(np.uint8, size).tobytes()
+    out = d_out.download(np.int8, n_set + 8)
+    for b in (d_buf, d_off, d_sz, d_first, d_out):
+        b.free()
+    assert (out[n_set:] == 0x55).all()   # nothing written past the n_set results
+    assert out[:n_set].tolist() == [w[0] for w in want]
+    if buf != bytes(after):
+        at = next(i for i in range(size) if buf[i] != after[i])
+        which = max((i for i in range(n) if off[i] <= at), default=-1)
+        raise AssertionError(f"byte {at} of the buffer differs: shred {which} starts at {off[which] if which >= 0 else None}")
+    return off
+
+
+def back_to_back(i, end):
+    return end + 16 if i == 0 else end

@@ -15,6 +15,7 @@ import fec_util
 import recover_model as model
 import recover_util as util
 import reedsol_model as rs
+from recover_util import back_to_back, expect, run_dev, written_d
 from shred_util import fixture
 
 pytestmark = pytest.mark.gpu
@@ -33,16 +34,6 @@ def eng(ed):
     e.close()
 
 
-def expect(sets, masks):
-    """the model's (code, slots) per set"""
-    return [model.fill(list(s), m) for s, m in zip(sets, masks)]
-
-
-def written_d(st, mask):
-    """data_cnt of the set's first received code shred"""
-    return next(int.from_bytes(s[0x53:0x55], "little") for s, e in zip(st, mask) if not e and s[0x40] & 0xF0 == 0x40)
-
-
 def check_host(eng, sets, masks, want=None):
     want = expect(sets, masks) if want is None else want
     codes, got = eng.fec_recover_host([list(s) for s in sets], masks)
@@ -50,69 +41,6 @@ def check_host(eng, sets, masks, want=None):
     for k, w in enumerate(want):
         assert [bytes(s) for s in got[k]] == list(w[1]), k
     return want
-
-
-def run_dev(eng, sets, masks, place, want=None, set_first=None):
-    """fd_ed25519_hip_fec_recover_dev on a device-resident buffer of guard
-    bytes in which place(i, end of the previous slot) says where slot i
-    starts -- an erased slot is guard bytes too, nothing of it is read --; the
-    whole buffer afterwards must be the same layout with exactly the bytes the
-    model writes changed: guard bytes, received slots, the proofs and tails of
-    erased slots unchanged"""
-    flat = [s for st in sets for s in st]
-    erased = [int(bool(e)) for m in masks for e in m]
-    n, n_set = len(flat), len(sets)
-    if set_first is None:
-        set_first = np.cumsum([0] + [len(s) for s in sets])
-    want = expect(sets, masks) if want is None else want
-    rng = random.Random(257)
-    off, end = [], 0
-    for i, s in enumerate(flat):
-        off.append(place(i, end))
-        assert off[-1] >= end
-        end = off[-1] + len(s)
-    size = end + 64
-    guard = rng.randbytes(size)
-    before, after = bytearray(guard), bytearray(guard)
-    i = 0
-    for st, mask, (code, filled) in zip(sets, masks, want):
-        d = written_d(st, mask) if code == 0 else 0
-        P = rs.region(len(st)) if st else 0
-        for j, (s, w, e) in enumerate(zip(st, filled, mask)):
-            o = off[i]
-            i += 1
-            if not e:
-                assert w == bytes(s)
-                before[o:o + len(s)] = s
-                after[o:o + len(s)] = s
-            elif code == 0:
-                # rule 12's bytes of an erased slot over the guard bytes; its proof and tail stay guard bytes
-                cut = (0x40 if j < d else 0x59) + P
-                after[o:o + 64] = w[:64]
-                after[o + 0x40:o + cut] = w[0x40:cut]
-    d_buf = eng.alloc(size).upload(np.frombuffer(bytes(before), np.uint8))
-    d_off = eng.alloc(8 * n + 8).upload(np.array(off + [0], np.uint64))
-    d_sz = eng.alloc(4 * n + 4).upload(np.array([len(s) for s in flat] + [0], np.uint32))
-    d_er = eng.alloc(n + 1).upload(np.array(erased + [0], np.uint8))
-    d_first = eng.alloc(4 * (n_set + 1)).upload(np.array(set_first, np.uint32))
-    d_out = eng.alloc(n_set + 8).upload(np.full(n_set + 8, 0x55, np.int8))
-    eng.fec_recover_dev(n, d_buf.ptr, d_off.ptr, d_sz.ptr, d_er.ptr, n_set, d_first.ptr, d_out.ptr)
-    eng.sync()
-    buf = d_buf.download(np.uint8, size).tobytes()
-    out = d_out.download(np.int8, n_set + 8)
-    for b in (d_buf, d_off, d_sz, d_er, d_first, d_out):
-        b.free()
-    assert (out[n_set:] == 0x55).all()   # nothing written past the n_set results
-    assert out[:n_set].tolist() == [w[0] for w in want]
-    if buf != bytes(after):
-        at = next(i for i in range(size) if buf[i] != after[i])
-        which = max((i for i in range(n) if off[i] <= at), default=-1)
-        raise AssertionError(f"byte {at} of the buffer differs: slot {which} starts at {off[which] if which >= 0 else None}")
-    return off
-
-
-def back_to_back(i, end):
-    return end + 16 if i == 0 else end
 
 
 def seal_and_verify(eng, sets):
