@@ -16,23 +16,20 @@
      matrix   log D_r per source and log N_e per target from the engine's
               log / exp tables (d additions each), then one coefficient
               L[e][r] = N_e / ((e ^ r) D_r) a lane into LDS
-     compare  the column loop over the received targets, the differences
-              OR-reduced over the workgroup: ERR_CORRUPT before any store
+     compare  the column loop (fd_reedsol_dev.h, fd_reedsol_rows) over the
+              received targets, the differences OR-reduced over the
+              workgroup: ERR_CORRUPT before any store
      headers  the first seven columns of the erased data shreds into LDS, and
               rule 11 on the data headers as they would stand
-     recover  the column loop over the erased targets: one lane per 4-byte
-              column, sources four at a time with load4_any from a per-source
-              offset kept in LDS (a data shred's region starts at 0x40, a code
-              shred's at 0x59), three selectors a dword, coefficients and
-              product tables from LDS at wave-uniform addresses, three
-              v_perm_b32 a product, FD_RC_ROWS accumulators a pass; then the
-              signature and, of a code shred, the header of every erased slot
+     recover  the column loop over the erased targets, the sources from a
+              per-source offset kept in LDS (a data shred's region starts at
+              0x40, a code shred's at 0x59); then the signature and, of a code
+              shred, the header of every erased slot
 
-   Stores follow the parity kernel's rule: a column is one dword when it is
-   dword-aligned and bytes when it is not, the three-byte last column always
-   bytes; bytes [0, 0x40) or [0, 0x59) of an erased slot go out as aligned
-   dwords wholly inside that range and bytes at its two ends.  No store covers
-   a byte outside what rule 12 names. */
+   The region's stores are the column loop's, under its one rule; bytes
+   [0, 0x40) or [0, 0x59) of an erased slot go out as aligned dwords wholly
+   inside that range and bytes at its two ends.  No store covers a byte
+   outside what rule 12 names. */
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "../../include/fd_ed25519_hip.h"
@@ -43,26 +40,23 @@
 #include "fd_reedsol_core.h"
 #include "fd_reedsol_dev.h"
 
-#define FD_RC_BLOCK   256   /* 255 columns at depth 6 (32+32), 250 at depth 7 */
-#define FD_RC_ROWS    32    /* targets a pass: their accumulators live in registers */
-#define FD_RC_STRIDE  68    /* a row of coefficients in LDS: 67 padded to whole dwords */
 #define FD_RC_ROW_MAX 160   /* at most 133 targets; a pass may start at any row and runs to a multiple of 8 behind it */
 #define FD_RC_HDR_COLS 7    /* the columns that hold a data shred's bytes [0x40, 0x59) */
 
 struct rc_lds_t {
   uint4    mul[FD_REEDSOL_CORE_MUL_BYTES / 16];          /* [256][2]: T0 T1 | T2 pad */
-  uint32_t coef[FD_RC_ROW_MAX * FD_RC_STRIDE / 4];       /* [target row][68], zero beyond the set's d and targets */
+  uint32_t coef[FD_RC_ROW_MAX * FD_REEDSOL_STRIDE / 4];  /* [target row][68], zero beyond the set's d and targets */
   uint64_t src[FD_REEDSOL_CORE_MAX + 1];                 /* where source i's region starts in p.shreds */
   uint32_t hdr[FD_REEDSOL_CORE_MAX * FD_RC_HDR_COLS];    /* bytes [0x40, 0x5c) of every data shred as after recovery */
   fd_reedsol_core_gf_t gf;
-  uint8_t  basis[FD_RC_STRIDE];                          /* the slot of source i */
-  uint8_t  log_d[FD_RC_STRIDE];
+  uint8_t  basis[FD_REEDSOL_STRIDE];                     /* the slot of source i */
+  uint8_t  log_d[FD_REEDSOL_STRIDE];
   uint8_t  tgt[FD_RC_ROW_MAX];                           /* the slot of target row r */
   uint8_t  log_n[FD_RC_ROW_MAX];
   uint8_t  erased[FD_FEC_CORE_CNT_MAX + 2];
   uint8_t  sig[64];                                      /* of the first received shred */
   uint8_t  ref[28];                                      /* bytes [0x40, 0x59) of the first received code shred */
-  uint64_t ballot[2][FD_RC_BLOCK / 64];                  /* received; erased data */
+  uint64_t ballot[2][FD_REEDSOL_BLOCK / 64];             /* received; erased data */
   uint32_t first_bad;    /* (j << 8 | code) of the first failing slot */
   uint32_t first_code;   /* the first received code shred the rules pass */
   uint32_t first_rcvd;
@@ -74,60 +68,17 @@ struct rc_lds_t {
 template <bool STORE>
 __device__ __forceinline__ uint32_t rc_rows(const fd_ed25519_fec_recover_params_t& p, const rc_lds_t& s, const uint64_t first,
                                             const uint32_t d, const uint32_t region, const uint32_t row0, const uint32_t row1) {
-  const uint32_t ncol = (region + 3u) >> 2;
-  uint32_t diff = 0u;
-  for (uint32_t col = threadIdx.x; col < ncol; col += FD_RC_BLOCK) {
-    for (uint32_t r0 = row0; r0 < row1; r0 += FD_RC_ROWS) {
-      uint32_t acc[FD_RC_ROWS];
-#pragma unroll
-      for (int r = 0; r < FD_RC_ROWS; r++) acc[r] = 0u;
-      for (uint32_t i0 = 0; i0 < d; i0 += 4) {
-        uint32_t s0[4], s1[4], s2[4];
-#pragma unroll
-        for (int u = 0; u < 4; u++) {
-          /* a column of the last region bytes may reach one byte into the proof: inside the shred */
-          const uint32_t x = i0 + u < d ? load4_any(p.shreds + s.src[i0 + u] + 4u * col) : 0u;
-          fd_reedsol_sel(x, s0[u], s1[u], s2[u]);
-        }
-#pragma unroll
-        for (int g = 0; g < FD_RC_ROWS; g += 8) {
-          if (r0 + g < row1) {   /* block-uniform; rows behind row1 are computed and dropped */
-#pragma unroll
-            for (int r = g; r < g + 8; r++) {
-              const uint32_t c4 = s.coef[(r0 + r) * (FD_RC_STRIDE / 4) + (i0 >> 2)];
-#pragma unroll
-              for (int u = 0; u < 4; u++) {
-                const uint32_t c = (c4 >> (8 * u)) & 0xffu;
-                acc[r] ^= fd_reedsol_mul(s.mul[2 * c], s.mul[2 * c + 1].x, s0[u], s1[u], s2[u]);
-              }
-            }
-          }
-        }
-      }
-#pragma unroll
-      for (int r = 0; r < FD_RC_ROWS; r++) {
-        if (r0 + r < row1) {
-          const uint32_t e = s.tgt[r0 + r];
-          uint8_t* dst = p.shreds + p.shred_off[first + e] + fd_reedsol_core_region_at(e, d) + 4u * col;
-          const uint32_t v = acc[r];
-          if (!STORE) {
-            diff |= (v ^ load4_any(dst)) & (col + 1u < ncol ? 0xffffffffu : 0x00ffffffu);   /* P = 3 mod 4 */
-          } else if (col + 1u < ncol && !(reinterpret_cast<uintptr_t>(dst) & 3)) {
-            *reinterpret_cast<uint32_t*>(dst) = v;
-          } else {
-            const uint32_t nb = col + 1u < ncol ? 4u : region - 4u * col;
-            for (uint32_t b = 0; b < nb; b++) dst[b] = (uint8_t)(v >> (8u * b));
-          }
-        }
-      }
-    }
-  }
-  return diff;
+  return fd_reedsol_rows<STORE>(
+      s.mul, s.coef, d, region, row0, row1, [&](const uint32_t i) { return p.shreds + s.src[i]; },
+      [&](const uint32_t r) {
+        const uint32_t e = s.tgt[r];
+        return p.shreds + p.shred_off[first + e] + fd_reedsol_core_region_at(e, d);
+      });
 }
 
 /* five waves a SIMD: 87 VGPRs without a spill where the compiler's own choice is 100 (four waves); measured 7 %
    faster on 4,096 sets of 32 + 32.  Six waves (80 VGPRs) spill. */
-__global__ void __launch_bounds__(FD_RC_BLOCK) __attribute__((amdgpu_waves_per_eu(5, 5)))
+__global__ void __launch_bounds__(FD_REEDSOL_BLOCK) __attribute__((amdgpu_waves_per_eu(5, 5)))
 fd_ed25519_fec_recover_kernel(fd_ed25519_fec_recover_params_t p) {
   __shared__ rc_lds_t s;
   const uint32_t k = blockIdx.x, t = threadIdx.x;
@@ -167,7 +118,7 @@ fd_ed25519_fec_recover_kernel(fd_ed25519_fec_recover_params_t p) {
   if ((t & 63u) == 0u) { s.ballot[0][t >> 6] = b_rcvd; s.ballot[1][t >> 6] = b_erd; }
   __syncthreads();
   uint32_t nrcv = 0u, ned = 0u, rank = 0u;
-  for (uint32_t w = 0; w < FD_RC_BLOCK / 64; w++) {
+  for (uint32_t w = 0; w < FD_REEDSOL_BLOCK / 64; w++) {
     const uint32_t c = (uint32_t)__popcll(s.ballot[0][w]);
     if (w < (t >> 6)) rank += c;
     nrcv += c;
@@ -197,12 +148,12 @@ fd_ed25519_fec_recover_kernel(fd_ed25519_fec_recover_params_t p) {
     }
   }
   const uint4* gmul = reinterpret_cast<const uint4*>(p.tab);
-  for (uint32_t q = t; q < FD_REEDSOL_CORE_MUL_BYTES / 16; q += FD_RC_BLOCK) s.mul[q] = gmul[q];
-  for (uint32_t q = t; q < FD_RC_ROW_MAX * FD_RC_STRIDE / 4; q += FD_RC_BLOCK) s.coef[q] = 0u;
+  for (uint32_t q = t; q < FD_REEDSOL_CORE_MUL_BYTES / 16; q += FD_REEDSOL_BLOCK) s.mul[q] = gmul[q];
+  for (uint32_t q = t; q < FD_RC_ROW_MAX * FD_REEDSOL_STRIDE / 4; q += FD_REEDSOL_BLOCK) s.coef[q] = 0u;
   {
     const uint32_t* ggf = reinterpret_cast<const uint32_t*>(p.tab + FD_REEDSOL_CORE_GF_AT);
     uint32_t* lgf = reinterpret_cast<uint32_t*>(&s.gf);
-    for (uint32_t q = t; q < sizeof(fd_reedsol_core_gf_t) / 4; q += FD_RC_BLOCK) lgf[q] = ggf[q];
+    for (uint32_t q = t; q < sizeof(fd_reedsol_core_gf_t) / 4; q += FD_REEDSOL_BLOCK) lgf[q] = ggf[q];
   }
   if (t < 64) s.sig[t] = p.shreds[p.shred_off[first + fr] + t];
   if (t < FD_REEDSOL_CORE_HDR_BYTES) s.ref[t] = p.shreds[p.shred_off[first + fc] + 0x40u + t];
@@ -211,9 +162,9 @@ fd_ed25519_fec_recover_kernel(fd_ed25519_fec_recover_params_t p) {
   if (t < ntgt) s.log_n[t] = (uint8_t)fd_reedsol_core_log_n(&s.gf, s.basis, d, s.tgt[t]);
   __syncthreads();
   uint8_t* coef8 = reinterpret_cast<uint8_t*>(s.coef);
-  for (uint32_t q = t; q < ntgt * d; q += FD_RC_BLOCK) {
+  for (uint32_t q = t; q < ntgt * d; q += FD_REEDSOL_BLOCK) {
     const uint32_t r = q / d, i = q % d;
-    coef8[r * FD_RC_STRIDE + i] = (uint8_t)fd_reedsol_core_coef(&s.gf, s.log_n[r], s.log_d[i], s.tgt[r], s.basis[i]);
+    coef8[r * FD_REEDSOL_STRIDE + i] = (uint8_t)fd_reedsol_core_coef(&s.gf, s.log_n[r], s.log_d[i], s.tgt[r], s.basis[i]);
   }
   __syncthreads();
 
@@ -222,7 +173,7 @@ fd_ed25519_fec_recover_kernel(fd_ed25519_fec_recover_params_t p) {
     const uint32_t diff = rc_rows<false>(p, s, first, d, region, 0u, ncmp);
     if (diff) atomicOr(&s.flag, 1u);
   }
-  for (uint32_t q = t; q < ned * 8u; q += FD_RC_BLOCK) {
+  for (uint32_t q = t; q < ned * 8u; q += FD_REEDSOL_BLOCK) {
     const uint32_t col = q & 7u, r = ncmp + (q >> 3);
     if (col < FD_RC_HDR_COLS) {
       uint32_t acc = 0u;
@@ -232,14 +183,14 @@ fd_ed25519_fec_recover_kernel(fd_ed25519_fec_recover_params_t p) {
         for (int u = 0; u < 8; u++) x[u] = i0 + u < d ? load4_any(p.shreds + s.src[i0 + u] + 4u * col) : 0u;
 #pragma unroll
         for (int u = 0; u < 8; u++) {
-          const uint32_t c = coef8[r * FD_RC_STRIDE + i0 + u];   /* zero beyond d */
+          const uint32_t c = coef8[r * FD_REEDSOL_STRIDE + i0 + u];   /* zero beyond d */
           acc ^= fd_reedsol_mul(s.mul[2 * c], s.mul[2 * c + 1].x, x[u] & 0x07070707u, (x[u] >> 3) & 0x07070707u, (x[u] >> 6) & 0x03030303u);
         }
       }
       s.hdr[s.tgt[r] * FD_RC_HDR_COLS + col] = acc;
     }
   }
-  for (uint32_t q = t; q < d * 8u; q += FD_RC_BLOCK) {
+  for (uint32_t q = t; q < d * 8u; q += FD_REEDSOL_BLOCK) {
     const uint32_t col = q & 7u, j = q >> 3;
     if (col < FD_RC_HDR_COLS && !s.erased[j])
       s.hdr[j * FD_RC_HDR_COLS + col] = load4_any(p.shreds + p.shred_off[first + j] + 0x40u + 4u * col);
@@ -272,7 +223,7 @@ fd_ed25519_fec_recover_kernel(fd_ed25519_fec_recover_params_t p) {
   rc_rows<true>(p, s, first, d, region, ncmp, ntgt);
   /* bytes [0, H) of an erased slot, H = 0x40 or 0x59: lane 0 of a slot's 24 has the bytes in front of the first
      aligned dword, lane q the dword q-1 behind it, or what is left of the range */
-  for (uint32_t q = t; q < (ntgt - ncmp) * 24u; q += FD_RC_BLOCK) {
+  for (uint32_t q = t; q < (ntgt - ncmp) * 24u; q += FD_REEDSOL_BLOCK) {
     const uint32_t e = s.tgt[ncmp + q / 24u], part = q % 24u;
     uint8_t* dst = p.shreds + p.shred_off[first + e];
     const uint32_t H = e < d ? 0x40u : FD_SHRED_CORE_CODE_HDR_SZ;
@@ -293,6 +244,6 @@ fd_ed25519_fec_recover_kernel(fd_ed25519_fec_recover_params_t p) {
 
 extern "C" int fd_ed25519_hip_launch_fec_recover(const fd_ed25519_fec_recover_params_t* p, void* stream) {
   if (!p->n_set) return 0;
-  hipLaunchKernelGGL(fd_ed25519_fec_recover_kernel, dim3((uint32_t)p->n_set), dim3(FD_RC_BLOCK), 0, (hipStream_t)stream, *p);
+  hipLaunchKernelGGL(fd_ed25519_fec_recover_kernel, dim3((uint32_t)p->n_set), dim3(FD_REEDSOL_BLOCK), 0, (hipStream_t)stream, *p);
   return (int)hipGetLastError();
 }

@@ -56,6 +56,20 @@
 /* nodes of every layer of the largest tree: 134+67+34+17+9+5+3+2+1 */
 #define FD_FEC_CORE_NODE_MAX  272U
 
+/* The shreds of the set [first, last) of a batch of n as the host wrappers
+   send it (fd_fec_pass.h): last - first, or 0 for a range that runs
+   backwards, leaves [0, n) or holds more than CNT_MAX shreds -- a set_first
+   that is no prefix sum.  0 is rule 1's ERR_SET, an empty range included,
+   and no shred of such a range is read or travels.  This is the cnt of the
+   three kernels (fd_ed25519_fec.hip, fd_ed25519_reedsol.hip,
+   fd_ed25519_recover.hip), whose range_ok is cnt != 0; they spell the
+   condition themselves, since taking it from here moved their scalar code
+   (profiles/fec_pass_ab.txt): change all four together. */
+FD_SHRED_FN unsigned
+fd_fec_core_set_cnt( unsigned long first, unsigned long last, unsigned long n ) {
+  return ( first<=last && last<=n && last-first<=FD_FEC_CORE_CNT_MAX ) ? (unsigned)( last-first ) : 0U;
+}
+
 /* fd_bmtree_depth( cnt ) - 1, the proof nodes of a leaf: cnt in [1,134] */
 FD_SHRED_FN unsigned
 fd_fec_core_depth( unsigned cnt ) {

@@ -4,7 +4,11 @@
    *_host ("The shape of a front"); and the rules the stage
    kernels run, on the host (*_count, *_plan, *_root, fec_parity, fec_recover, poh, poh_prepare).  Part of the engine:
    the *_host wrappers stage in its pinned buffers
-   (fd_ed25519_hip_engine_fields.h). */
+   (fd_ed25519_hip_engine_fields.h).  The three wrappers over whole FEC sets
+   (fec_seal_host, fec_parity_host, fec_recover_host) share one pass by sets
+   -- cut, room, stage; upload; *_dev; download and the front's own copy-back
+   -- whose cut, in-block layout and staging are plain C in ../fd_fec_pass.h,
+   held to their buffers under ASan and UBSan by tests/fec_pass_main.c. */
 
 #define _GNU_SOURCE
 #include "fd_ed25519_hip_engine_fields.h"
@@ -18,6 +22,7 @@
 #include "../fd_reedsol_core.h"
 #include "../fd_poh_core.h"
 #include "../fd_front_work.h"
+#include "../fd_fec_pass.h"
 
 #include <stdlib.h>
 #include <string.h>
@@ -561,14 +566,50 @@ fd_ed25519_hip_fec_seal_dev( fd_ed25519_hip_engine_t * e, unsigned long n, unsig
   return FD_ED25519_HIP_OK;
 }
 
-/* Pass by pass, whole sets at a time: up to FRONT_HOST_CHUNK shreds and as
-   many sets.  A set whose range runs backwards, leaves [0, n) or holds more
-   than FEC_SET_MAX shreds travels as an empty set, which is the same code.
-   No rule reads and no kernel writes a byte at or past FD_SHRED_MAX_SZ, so a
-   longer shred travels as its head and its true size.
-   in: privs [ms][32], off u64 [m], set_first u32 [ms+1], sz u32 [m];
-   out: roots [ms][32], sigs [ms][64], codes [ms].  Of a sealed set's shreds
-   the signature (with privs) and the proof are copied back, nothing else. */
+/* ---- a pass by sets: what the three FEC-set wrappers do alike (fd_fec_pass.h) -- */
+
+_Static_assert( FD_FEC_PASS_CHUNK==FRONT_HOST_CHUNK, "a pass by sets is bounded as a pass by items" );
+
+typedef struct {
+  uint64_t             k1, m, ms;   /* the pass is the sets [k0, k1): ms sets, m shreds */
+  fd_fec_pass_in_t     at;          /* its in block */
+  fd_fec_pass_staged_t sg;          /* its item staging */
+} fec_pass_t;
+
+/* cut, room, stage: the pass from set k0 into the pinned staging, with room for out_per_set bytes a set to come back */
+static int
+fec_pass_begin( fd_ed25519_hip_engine_t * e, int front, unsigned long n, unsigned char const * shreds,
+                unsigned long const * shred_off, unsigned int const * shred_sz, unsigned char const * erased,
+                unsigned long n_set, unsigned int const * set_first, unsigned char const * privs, uint64_t k0,
+                uint64_t out_per_set, fec_pass_t * ps ) {
+  ps->m  = fd_fec_pass_cut( set_first, n_set, n, k0, &ps->k1 );
+  ps->ms = ps->k1-k0;
+  ps->at = fd_fec_pass_in( ps->m, ps->ms, privs!=NULL, front==FD_FEC_PASS_RECOVER );
+  int err = front_room( e, fd_fec_pass_item_bytes( front, ps->m ), ps->at.in_bytes, out_per_set*ps->ms );
+  if( err ) return err;
+  if( privs ) memcpy( e->h_fr_in + ps->at.keys_at, privs + 32UL*k0, 32UL*ps->ms );
+  ps->sg = fd_fec_pass_stage( front, shreds, shred_off, shred_sz, erased, n, set_first, k0, ps->k1, e->h_msgs, e->h_fr_in, &ps->at );
+  return FD_ED25519_HIP_OK;
+}
+
+/* the pass's arrays on the device, as the *_dev take them */
+#define FEC_PASS_D_OFF( e, ps )   ( (unsigned long const *)( (e)->d_fr_in + (ps).at.off_at ) )
+#define FEC_PASS_D_FIRST( e, ps ) ( (unsigned int const *)( (e)->d_fr_in + (ps).at.first_at ) )
+#define FEC_PASS_D_SZ( e, ps )    ( (unsigned int const *)( (e)->d_fr_in + (ps).at.sz_at ) )
+
+/* the aside slots, which the kernel has filled, back into the pinned staging */
+static int
+fec_pass_aside_down( fd_ed25519_hip_engine_t * e, fec_pass_t const * ps, hipStream_t st ) {
+  if( ps->sg.n_aside )
+    HIPCHK( hipMemcpyAsync( e->h_msgs + ps->sg.aside_at, e->d_msgs + ps->sg.aside_at, FD_SHRED_CORE_MAX_SZ*ps->sg.n_aside,
+                            hipMemcpyDeviceToHost, st ), "D2H aside shreds" );
+  return FD_ED25519_HIP_OK;
+}
+
+/* Pass by pass (fd_fec_pass.h): no shred stands aside, all come down.  The
+   keys, with privs, stand in front of the in block; out: roots [ms][32],
+   sigs [ms][64], codes [ms].  Of a sealed set's shreds the signature (with
+   privs) and the proof are copied back, nothing else. */
 int
 fd_ed25519_hip_fec_seal_host( fd_ed25519_hip_engine_t * e, unsigned long n, unsigned char * shreds,
                               unsigned long const * shred_off, unsigned int const * shred_sz, unsigned long n_set,
@@ -578,61 +619,35 @@ fd_ed25519_hip_fec_seal_host( fd_ed25519_hip_engine_t * e, unsigned long n, unsi
   int err = front_begin( e, n_set, set_first && set_out && ( !n || ( shreds && shred_off && shred_sz ) ) && n<=UINT32_MAX &&
                                    ( privs || !sigs ), 0UL, NULL, NULL, &st );
   if( err<=0 ) return err;
-  for( uint64_t k0=0UL; k0<n_set; ) {
-    uint64_t k1 = k0, m = 0UL;
-    for( ; k1<n_set && k1-k0<FRONT_HOST_CHUNK; k1++ ) {
-      uint64_t first = set_first[k1], last = set_first[k1+1UL];
-      uint64_t cnt = ( first<=last && last<=n && last-first<=FD_FEC_CORE_CNT_MAX ) ? last-first : 0UL;
-      if( m+cnt>FRONT_HOST_CHUNK ) break;
-      m += cnt;
-    }
-    uint64_t ms = k1-k0, priv_bytes = privs ? 32UL*ms : 0UL;
-    uint64_t off_at = priv_bytes, first_at = off_at + 8UL*m, sz_at = first_at + 4UL*( ms+1UL ), in_bytes = sz_at + 4UL*m;
-    uint64_t sigs_at = 32UL*ms, codes_at = 96UL*ms, out_bytes = 97UL*ms;
-    if( (err = front_room( e, m*FD_SHRED_CORE_MAX_SZ, in_bytes, out_bytes )) ) return err;
-    uint64_t * h_off   = (uint64_t *)( e->h_fr_in + off_at );
-    uint32_t * h_first = (uint32_t *)( e->h_fr_in + first_at );
-    uint32_t * h_sz    = (uint32_t *)( e->h_fr_in + sz_at );
-    if( privs ) memcpy( e->h_fr_in, privs + 32UL*k0, priv_bytes );
-    uint64_t pos = 0UL, i = 0UL;
-    for( uint64_t k=k0; k<k1; k++ ) {
-      uint64_t first = set_first[k], last = set_first[k+1UL];
-      uint64_t cnt = ( first<=last && last<=n && last-first<=FD_FEC_CORE_CNT_MAX ) ? last-first : 0UL;
-      h_first[ k-k0 ] = (uint32_t)i;
-      for( uint64_t j=first; j<first+cnt; j++, i++ ) {
-        uint64_t cp = shred_sz[j]<=FD_SHRED_CORE_MAX_SZ ? shred_sz[j] : FD_SHRED_CORE_MAX_SZ;
-        if( cp ) memcpy( e->h_msgs + pos, shreds + shred_off[j], cp );
-        h_off[i] = pos;
-        h_sz [i] = shred_sz[j];
-        pos += cp;
-      }
-    }
-    h_first[ ms ] = (uint32_t)i;
-    if( (err = grow_dev( &e->d_fr_work, &e->fr_work_cap, FD_ED25519_HIP_FEC_WORK_BYTES( m, ms ) )) ) return err;
-    if( (err = front_upload( e, pos, in_bytes, st )) ) return err;
-    err = fd_ed25519_hip_fec_seal_dev( e, m, e->d_msgs, (unsigned long const *)( e->d_fr_in + off_at ),
-                                       (unsigned int const *)( e->d_fr_in + sz_at ), ms,
-                                       (unsigned int const *)( e->d_fr_in + first_at ), privs ? e->d_fr_in : NULL,
-                                       e->d_fr_work, (signed char *)( e->d_fr_out + codes_at ), e->d_fr_out,
+  fec_pass_t ps;
+  for( uint64_t k0=0UL; k0<n_set; k0=ps.k1 ) {
+    if( (err = fec_pass_begin( e, FD_FEC_PASS_SEAL, n, shreds, shred_off, shred_sz, NULL, n_set, set_first, privs, k0, 97UL, &ps )) )
+      return err;
+    uint64_t ms = ps.ms, sigs_at = 32UL*ms, codes_at = 96UL*ms;
+    if( (err = grow_dev( &e->d_fr_work, &e->fr_work_cap, FD_ED25519_HIP_FEC_WORK_BYTES( ps.m, ms ) )) ) return err;
+    if( (err = front_upload( e, ps.sg.whole, ps.at.in_bytes, st )) ) return err;
+    err = fd_ed25519_hip_fec_seal_dev( e, ps.m, e->d_msgs, FEC_PASS_D_OFF( e, ps ), FEC_PASS_D_SZ( e, ps ), ms,
+                                       FEC_PASS_D_FIRST( e, ps ), privs ? e->d_fr_in + ps.at.keys_at : NULL, e->d_fr_work,
+                                       (signed char *)( e->d_fr_out + codes_at ), e->d_fr_out,
                                        privs ? e->d_fr_out + sigs_at : NULL, st );
     if( err ) return err;
-    if( pos ) HIPCHK( hipMemcpyAsync( e->h_msgs, e->d_msgs, pos, hipMemcpyDeviceToHost, st ), "D2H sealed shreds" );
-    if( (err = front_download( e, out_bytes, st )) ) return err;
+    if( ps.sg.whole )
+      HIPCHK( hipMemcpyAsync( e->h_msgs, e->d_msgs, ps.sg.whole, hipMemcpyDeviceToHost, st ), "D2H sealed shreds" );
+    if( (err = front_download( e, 97UL*ms, st )) ) return err;
     memcpy( set_out + k0, e->h_fr_out + codes_at, ms );
     if( roots ) memcpy( roots + 32UL*k0, e->h_fr_out, 32UL*ms );
     if( sigs )  memcpy( sigs  + 64UL*k0, e->h_fr_out + sigs_at, 64UL*ms );
-    for( uint64_t k=k0; k<k1; k++ ) {
+    for( uint64_t k=k0; k<ps.k1; k++ ) {
       if( set_out[k] ) continue;                      /* rule 6 */
       uint64_t first = set_first[k], cnt = set_first[k+1UL]-first, depth = fd_fec_core_depth( (unsigned)cnt );
       for( uint64_t j=0UL; j<cnt; j++ ) {
         unsigned char *       dst = shreds + shred_off[ first+j ];
-        unsigned char const * src = e->h_msgs + h_off[ h_first[ k-k0 ]+j ];
+        unsigned char const * src = e->h_msgs + fd_fec_pass_at( e->h_fr_in, &ps.at, k-k0, j );
         uint64_t proof_at = ( ( src[ 0x40 ] & 0xf0 )==0x80 ? FD_SHRED_CORE_MIN_SZ : FD_SHRED_CORE_MAX_SZ ) - 20UL*depth;
         if( privs ) memcpy( dst, src, 64UL );
         memcpy( dst + proof_at, src + proof_at, 20UL*depth );
       }
     }
-    k0 = k1;
   }
   return FD_ED25519_HIP_OK;
 }
@@ -667,23 +682,11 @@ fd_ed25519_hip_fec_parity_dev( fd_ed25519_hip_engine_t * e, unsigned long n, uns
   return FD_ED25519_HIP_OK;
 }
 
-/* a shred that travels as its header: a code shred (type 0x4?) keeps its
-   1228 bytes on the device, where the kernel fills them, and sends its first
-   0x59 -- no rule reads a byte at or past 0x59 */
-static int
-parity_travels_as_header( unsigned char const * s, uint64_t sz ) {
-  return sz>0x40UL && ( s[ 0x40 ] & 0xf0 )==0x40;
-}
-
-/* Pass by pass, whole sets at a time, as fec_seal_host.  A pass's staging,
-   the same on the host and on the device: the shreds that travel whole back
-   to back (the data shreds; capped at FD_SHRED_MAX_SZ as the seal's), then,
-   from the next 16-byte boundary, the code shreds 1228 bytes apart.  Up go
-   the first part as it is and bytes [0, 0x59) of every code shred (one
-   strided copy); down comes the second part.
-   in: off u64 [m], set_first u32 [ms+1], sz u32 [m]; out: codes [ms].  Of a
-   set with code 0 the parity regions of its code shreds are copied back,
-   nothing else. */
+/* Pass by pass (fd_fec_pass.h): the code shreds stand aside.  Up go the
+   whole shreds as they are and bytes [0, 0x59) of every code shred (one
+   strided copy); down come the code shreds.  out: codes [ms].  Of a set with
+   code 0 the parity regions of its code shreds are copied back, nothing
+   else. */
 int
 fd_ed25519_hip_fec_parity_host( fd_ed25519_hip_engine_t * e, unsigned long n, unsigned char * shreds,
                                 unsigned long const * shred_off, unsigned int const * shred_sz, unsigned long n_set,
@@ -692,75 +695,30 @@ fd_ed25519_hip_fec_parity_host( fd_ed25519_hip_engine_t * e, unsigned long n, un
   int err = front_begin( e, n_set, set_first && set_out && ( !n || ( shreds && shred_off && shred_sz ) ) && n<=UINT32_MAX,
                          0UL, NULL, NULL, &st );
   if( err<=0 ) return err;
-  for( uint64_t k0=0UL; k0<n_set; ) {
-    uint64_t k1 = k0, m = 0UL;
-    for( ; k1<n_set && k1-k0<FRONT_HOST_CHUNK; k1++ ) {
-      uint64_t first = set_first[k1], last = set_first[k1+1UL];
-      uint64_t cnt = ( first<=last && last<=n && last-first<=FD_FEC_CORE_CNT_MAX ) ? last-first : 0UL;
-      if( m+cnt>FRONT_HOST_CHUNK ) break;
-      m += cnt;
-    }
-    uint64_t ms = k1-k0;
-    uint64_t first_at = 8UL*m, sz_at = first_at + 4UL*( ms+1UL ), in_bytes = sz_at + 4UL*m;
-    if( (err = front_room( e, m*FD_SHRED_CORE_MAX_SZ + 16UL, in_bytes, ms )) ) return err;
-    uint64_t * h_off   = (uint64_t *)e->h_fr_in;
-    uint32_t * h_first = (uint32_t *)( e->h_fr_in + first_at );
-    uint32_t * h_sz    = (uint32_t *)( e->h_fr_in + sz_at );
-    /* the whole shreds first: where they end, the code shreds begin */
-    uint64_t whole = 0UL, i = 0UL;
-    for( uint64_t k=k0; k<k1; k++ ) {
-      uint64_t first = set_first[k], last = set_first[k+1UL];
-      uint64_t cnt = ( first<=last && last<=n && last-first<=FD_FEC_CORE_CNT_MAX ) ? last-first : 0UL;
-      for( uint64_t j=first; j<first+cnt; j++ )
-        if( !parity_travels_as_header( shreds + shred_off[j], shred_sz[j] ) )
-          whole += shred_sz[j]<=FD_SHRED_CORE_MAX_SZ ? shred_sz[j] : FD_SHRED_CORE_MAX_SZ;
-    }
-    uint64_t code_at = ( whole+15UL ) & ~15UL, pos = 0UL, n_code = 0UL;
-    for( uint64_t k=k0; k<k1; k++ ) {
-      uint64_t first = set_first[k], last = set_first[k+1UL];
-      uint64_t cnt = ( first<=last && last<=n && last-first<=FD_FEC_CORE_CNT_MAX ) ? last-first : 0UL;
-      h_first[ k-k0 ] = (uint32_t)i;
-      for( uint64_t j=first; j<first+cnt; j++, i++ ) {
-        unsigned char const * s = shreds + shred_off[j];
-        h_sz[i] = shred_sz[j];
-        if( parity_travels_as_header( s, shred_sz[j] ) ) {
-          uint64_t cp = shred_sz[j]<FD_SHRED_CORE_CODE_HDR_SZ ? shred_sz[j] : FD_SHRED_CORE_CODE_HDR_SZ;
-          h_off[i] = code_at + FD_SHRED_CORE_MAX_SZ*n_code++;
-          memset( e->h_msgs + h_off[i], 0, FD_SHRED_CORE_CODE_HDR_SZ );
-          memcpy( e->h_msgs + h_off[i], s, cp );
-        } else {
-          uint64_t cp = shred_sz[j]<=FD_SHRED_CORE_MAX_SZ ? shred_sz[j] : FD_SHRED_CORE_MAX_SZ;
-          if( cp ) memcpy( e->h_msgs + pos, s, cp );
-          h_off[i] = pos;
-          pos += cp;
-        }
-      }
-    }
-    h_first[ ms ] = (uint32_t)i;
-    if( (err = front_upload( e, pos, in_bytes, st )) ) return err;
-    if( n_code )
-      HIPCHK( hipMemcpy2DAsync( e->d_msgs + code_at, FD_SHRED_CORE_MAX_SZ, e->h_msgs + code_at, FD_SHRED_CORE_MAX_SZ,
-                                FD_SHRED_CORE_CODE_HDR_SZ, n_code, hipMemcpyHostToDevice, st ), "H2D parity headers" );
-    err = fd_ed25519_hip_fec_parity_dev( e, m, e->d_msgs, (unsigned long const *)e->d_fr_in,
-                                         (unsigned int const *)( e->d_fr_in + sz_at ), ms,
-                                         (unsigned int const *)( e->d_fr_in + first_at ), (signed char *)e->d_fr_out, st );
+  fec_pass_t ps;
+  for( uint64_t k0=0UL; k0<n_set; k0=ps.k1 ) {
+    if( (err = fec_pass_begin( e, FD_FEC_PASS_PARITY, n, shreds, shred_off, shred_sz, NULL, n_set, set_first, NULL, k0, 1UL, &ps )) )
+      return err;
+    if( (err = front_upload( e, ps.sg.whole, ps.at.in_bytes, st )) ) return err;
+    if( ps.sg.n_aside )
+      HIPCHK( hipMemcpy2DAsync( e->d_msgs + ps.sg.aside_at, FD_SHRED_CORE_MAX_SZ, e->h_msgs + ps.sg.aside_at, FD_SHRED_CORE_MAX_SZ,
+                                FD_SHRED_CORE_CODE_HDR_SZ, ps.sg.n_aside, hipMemcpyHostToDevice, st ), "H2D parity headers" );
+    err = fd_ed25519_hip_fec_parity_dev( e, ps.m, e->d_msgs, FEC_PASS_D_OFF( e, ps ), FEC_PASS_D_SZ( e, ps ), ps.ms,
+                                         FEC_PASS_D_FIRST( e, ps ), (signed char *)e->d_fr_out, st );
     if( err ) return err;
-    if( n_code )
-      HIPCHK( hipMemcpyAsync( e->h_msgs + code_at, e->d_msgs + code_at, FD_SHRED_CORE_MAX_SZ*n_code, hipMemcpyDeviceToHost, st ),
-              "D2H parity shreds" );
-    if( (err = front_download( e, ms, st )) ) return err;
-    memcpy( set_out + k0, e->h_fr_out, ms );
-    for( uint64_t k=k0; k<k1; k++ ) {
+    if( (err = fec_pass_aside_down( e, &ps, st )) ) return err;
+    if( (err = front_download( e, ps.ms, st )) ) return err;
+    memcpy( set_out + k0, e->h_fr_out, ps.ms );
+    for( uint64_t k=k0; k<ps.k1; k++ ) {
       if( set_out[k] ) continue;                      /* rule 8 */
       uint64_t first = set_first[k], cnt = set_first[k+1UL]-first;
       uint64_t region = FD_REEDSOL_CORE_REGION( fd_fec_core_depth( (unsigned)cnt ) );
       for( uint64_t j=0UL; j<cnt; j++ ) {
-        uint64_t at = h_off[ h_first[ k-k0 ]+j ];
-        if( at<code_at ) continue;                    /* a data shred: read only */
+        uint64_t at = fd_fec_pass_at( e->h_fr_in, &ps.at, k-k0, j );
+        if( at<ps.sg.aside_at ) continue;             /* a data shred: read only */
         memcpy( shreds + shred_off[ first+j ] + FD_SHRED_CORE_CODE_HDR_SZ, e->h_msgs + at + FD_SHRED_CORE_CODE_HDR_SZ, region );
       }
     }
-    k0 = k1;
   }
   return FD_ED25519_HIP_OK;
 }
@@ -792,14 +750,10 @@ fd_ed25519_hip_fec_recover_dev( fd_ed25519_hip_engine_t * e, unsigned long n, un
   return FD_ED25519_HIP_OK;
 }
 
-/* Pass by pass, whole sets at a time, as fec_parity_host.  A pass's staging,
-   the same on the host and on the device: the received slots back to back
-   (capped at FD_SHRED_MAX_SZ as the seal's), then, from the next 16-byte
-   boundary, the erased slots 1228 bytes apart, of which nothing goes up --
-   the kernel reads an erased slot's size alone -- and all comes down.
-   in: off u64 [m], set_first u32 [ms+1], sz u32 [m], erased u8 [m]; out:
-   codes [ms].  Of a set with code 0 the bytes rule 12 names of its erased
-   slots are copied back, nothing else. */
+/* Pass by pass (fd_fec_pass.h): the erased slots stand aside, nothing of
+   them goes up and all of them come down; the erased flags stand behind the
+   in block.  out: codes [ms].  Of a set with code 0 the bytes rule 12 names
+   of its erased slots are copied back, nothing else. */
 int
 fd_ed25519_hip_fec_recover_host( fd_ed25519_hip_engine_t * e, unsigned long n, unsigned char * shreds,
                                  unsigned long const * shred_off, unsigned int const * shred_sz, unsigned char const * erased,
@@ -808,59 +762,18 @@ fd_ed25519_hip_fec_recover_host( fd_ed25519_hip_engine_t * e, unsigned long n, u
   int err = front_begin( e, n_set, set_first && set_out && ( !n || ( shreds && shred_off && shred_sz && erased ) ) &&
                                    n<=UINT32_MAX, 0UL, NULL, NULL, &st );
   if( err<=0 ) return err;
-  for( uint64_t k0=0UL; k0<n_set; ) {
-    uint64_t k1 = k0, m = 0UL;
-    for( ; k1<n_set && k1-k0<FRONT_HOST_CHUNK; k1++ ) {
-      uint64_t first = set_first[k1], last = set_first[k1+1UL];
-      uint64_t cnt = ( first<=last && last<=n && last-first<=FD_FEC_CORE_CNT_MAX ) ? last-first : 0UL;
-      if( m+cnt>FRONT_HOST_CHUNK ) break;
-      m += cnt;
-    }
-    uint64_t ms = k1-k0;
-    uint64_t first_at = 8UL*m, sz_at = first_at + 4UL*( ms+1UL ), er_at = sz_at + 4UL*m, in_bytes = er_at + m;
-    if( (err = front_room( e, m*FD_SHRED_CORE_MAX_SZ + 16UL, in_bytes, ms )) ) return err;
-    uint64_t * h_off   = (uint64_t *)e->h_fr_in;
-    uint32_t * h_first = (uint32_t *)( e->h_fr_in + first_at );
-    uint32_t * h_sz    = (uint32_t *)( e->h_fr_in + sz_at );
-    uint8_t *  h_er    = e->h_fr_in + er_at;
-    /* the received slots first: where they end, the erased slots begin */
-    uint64_t whole = 0UL, i = 0UL;
-    for( uint64_t k=k0; k<k1; k++ ) {
-      uint64_t first = set_first[k], last = set_first[k+1UL];
-      uint64_t cnt = ( first<=last && last<=n && last-first<=FD_FEC_CORE_CNT_MAX ) ? last-first : 0UL;
-      for( uint64_t j=first; j<first+cnt; j++ )
-        if( !erased[j] ) whole += shred_sz[j]<=FD_SHRED_CORE_MAX_SZ ? shred_sz[j] : FD_SHRED_CORE_MAX_SZ;
-    }
-    uint64_t er_base = ( whole+15UL ) & ~15UL, pos = 0UL, n_er = 0UL;
-    for( uint64_t k=k0; k<k1; k++ ) {
-      uint64_t first = set_first[k], last = set_first[k+1UL];
-      uint64_t cnt = ( first<=last && last<=n && last-first<=FD_FEC_CORE_CNT_MAX ) ? last-first : 0UL;
-      h_first[ k-k0 ] = (uint32_t)i;
-      for( uint64_t j=first; j<first+cnt; j++, i++ ) {
-        h_sz[i] = shred_sz[j];
-        h_er[i] = erased[j]!=0U;
-        if( erased[j] ) {
-          h_off[i] = er_base + FD_SHRED_CORE_MAX_SZ*n_er++;
-        } else {
-          uint64_t cp = shred_sz[j]<=FD_SHRED_CORE_MAX_SZ ? shred_sz[j] : FD_SHRED_CORE_MAX_SZ;
-          if( cp ) memcpy( e->h_msgs + pos, shreds + shred_off[j], cp );
-          h_off[i] = pos;
-          pos += cp;
-        }
-      }
-    }
-    h_first[ ms ] = (uint32_t)i;
-    if( (err = front_upload( e, pos, in_bytes, st )) ) return err;
-    err = fd_ed25519_hip_fec_recover_dev( e, m, e->d_msgs, (unsigned long const *)e->d_fr_in,
-                                          (unsigned int const *)( e->d_fr_in + sz_at ), e->d_fr_in + er_at, ms,
-                                          (unsigned int const *)( e->d_fr_in + first_at ), (signed char *)e->d_fr_out, st );
+  fec_pass_t ps;
+  for( uint64_t k0=0UL; k0<n_set; k0=ps.k1 ) {
+    if( (err = fec_pass_begin( e, FD_FEC_PASS_RECOVER, n, shreds, shred_off, shred_sz, erased, n_set, set_first, NULL, k0, 1UL, &ps )) )
+      return err;
+    if( (err = front_upload( e, ps.sg.whole, ps.at.in_bytes, st )) ) return err;
+    err = fd_ed25519_hip_fec_recover_dev( e, ps.m, e->d_msgs, FEC_PASS_D_OFF( e, ps ), FEC_PASS_D_SZ( e, ps ),
+                                          e->d_fr_in + ps.at.flags_at, ps.ms, FEC_PASS_D_FIRST( e, ps ), (signed char *)e->d_fr_out, st );
     if( err ) return err;
-    if( n_er )
-      HIPCHK( hipMemcpyAsync( e->h_msgs + er_base, e->d_msgs + er_base, FD_SHRED_CORE_MAX_SZ*n_er, hipMemcpyDeviceToHost, st ),
-              "D2H recovered shreds" );
-    if( (err = front_download( e, ms, st )) ) return err;
-    memcpy( set_out + k0, e->h_fr_out, ms );
-    for( uint64_t k=k0; k<k1; k++ ) {
+    if( (err = fec_pass_aside_down( e, &ps, st )) ) return err;
+    if( (err = front_download( e, ps.ms, st )) ) return err;
+    memcpy( set_out + k0, e->h_fr_out, ps.ms );
+    for( uint64_t k=k0; k<ps.k1; k++ ) {
       if( set_out[k] ) continue;                      /* rule 12 */
       uint64_t first = set_first[k], cnt = set_first[k+1UL]-first;
       uint64_t region = FD_REEDSOL_CORE_REGION( fd_fec_core_depth( (unsigned)cnt ) );
@@ -873,13 +786,12 @@ fd_ed25519_hip_fec_recover_host( fd_ed25519_hip_engine_t * e, unsigned long n, u
         }
       for( uint64_t j=0UL; j<cnt; j++ ) {
         if( !erased[ first+j ] ) continue;            /* a received slot: read only */
-        unsigned char const * from = e->h_msgs + h_off[ h_first[ k-k0 ]+j ];
+        unsigned char const * from = e->h_msgs + fd_fec_pass_at( e->h_fr_in, &ps.at, k-k0, j );
         unsigned char *       to   = shreds + shred_off[ first+j ];
         if( j<d ) { memcpy( to, from, 64UL ); memcpy( to + 0x40UL, from + 0x40UL, region ); }
         else      memcpy( to, from, FD_SHRED_CORE_CODE_HDR_SZ + region );
       }
     }
-    k0 = k1;
   }
   return FD_ED25519_HIP_OK;
 }

@@ -630,6 +630,29 @@ class Engine:
                                             d_val_first, int(n_val), d_work, d_pkt_out, d_val_out, d_sig_out, d_hash_out,
                                             stream))
 
+    def _fec_flat(self, shreds, set_first, call):
+        """What the three fec_*_flat share: packs shreds, runs call(n, shreds,
+        off, sz, n_set, set_first, codes) -- a *_host of the library over those
+        pointers -- and unpacks -> (int8 code per set, the shreds after)."""
+        from .tile import pack_payloads
+        n, n_set = len(shreds), len(set_first) - 1
+        first = _c(set_first, np.uint32)
+        codes = np.zeros(max(1, n_set), np.int8)
+        buf, off, sz = pack_payloads([bytes(s) for s in shreds]) if n else (np.zeros(1, np.uint8),) * 3
+        _check(call(n, _ptr(buf), _ptr(off), _ptr(sz), n_set, _ptr(first), _ptr(codes)))
+        return codes[:n_set], [buf[int(off[i]):int(off[i]) + int(sz[i])].tobytes() for i in range(n)]
+
+    @staticmethod
+    def _fec_by_sets(sets, flat_call):
+        """What the three fec_*_host share: flattens sets, runs flat_call(the
+        shreds, their set_first) -- a fec_*_flat -- and splits the shreds it
+        returns (its second result) into sets again."""
+        first = [0]
+        for s in sets:
+            first.append(first[-1] + len(s))
+        codes, flat, *rest = flat_call([x for s in sets for x in s], first)
+        return (codes, [flat[first[k]:first[k + 1]] for k in range(len(sets))], *rest)
+
     def fec_seal_flat(self, shreds, set_first, privs):
         """fd_ed25519_hip_fec_seal_host on shreds (a list of raw shreds) whose
         set k is shreds[set_first[k]:set_first[k + 1]] in tree order; privs is
@@ -637,10 +660,8 @@ class Engine:
         roots only) -> (int8 code per set, the shreds after the call, uint8
         [n_set, 32] roots, uint8 [n_set, 64] signatures or None);
         synchronous."""
-        from .tile import pack_payloads
-        n, n_set = len(shreds), len(set_first) - 1
-        first = _c(set_first, np.uint32)
-        codes, roots = np.zeros(max(1, n_set), np.int8), np.zeros((max(1, n_set), 32), np.uint8)
+        n_set = len(set_first) - 1
+        roots = np.zeros((max(1, n_set), 32), np.uint8)
         keys = sigs = None
         if privs is not None:
             if isinstance(privs, (bytes, bytearray)):
@@ -648,11 +669,9 @@ class Engine:
             keys = np.frombuffer(b"".join(bytes(k) for k in privs) or bytes(32), np.uint8)
             assert keys.size == 32 * max(1, n_set)
             sigs = np.zeros((max(1, n_set), 64), np.uint8)
-        buf, off, sz = pack_payloads([bytes(s) for s in shreds]) if n else (np.zeros(1, np.uint8),) * 3
-        _check(_lib.fd_ed25519_hip_fec_seal_host(self._h, n, _ptr(buf), _ptr(off), _ptr(sz), n_set, _ptr(first), _ptr(keys),
-                                                 _ptr(codes), _ptr(roots), _ptr(sigs)))
-        out = [buf[int(off[i]):int(off[i]) + int(sz[i])].tobytes() for i in range(n)]
-        return codes[:n_set], out, roots[:n_set], (sigs[:n_set] if sigs is not None else None)
+        codes, out = self._fec_flat(shreds, set_first, lambda n, buf, off, sz, ns, first, codes: _lib.fd_ed25519_hip_fec_seal_host(
+            self._h, n, buf, off, sz, ns, first, _ptr(keys), codes, _ptr(roots), _ptr(sigs)))
+        return codes, out, roots[:n_set], (sigs[:n_set] if sigs is not None else None)
 
     def fec_seal_host(self, sets, privs):
         """Seals FEC sets (fd_ed25519_hip_fec_seal_host): sets is a list of
@@ -660,11 +679,7 @@ class Engine:
         parity), privs as for fec_seal_flat -> (int8 code per set, the sets
         with signature and proofs written where the code is 0, roots,
         signatures or None); synchronous."""
-        first = [0]
-        for s in sets:
-            first.append(first[-1] + len(s))
-        codes, flat, roots, sigs = self.fec_seal_flat([x for s in sets for x in s], first, privs)
-        return codes, [flat[first[k]:first[k + 1]] for k in range(len(sets))], roots, sigs
+        return self._fec_by_sets(sets, lambda flat, first: self.fec_seal_flat(flat, first, privs))
 
     def fec_seal_dev(self, n, d_shreds, d_off, d_sz, n_set, d_set_first, d_privs, d_work, d_set_out, d_roots=None,
                      d_sigs=None, stream=None):
@@ -676,13 +691,8 @@ class Engine:
         """fd_ed25519_hip_fec_parity_host on shreds (a list of raw shreds)
         whose set k is shreds[set_first[k]:set_first[k + 1]] in tree order ->
         (int8 code per set, the shreds after the call); synchronous."""
-        from .tile import pack_payloads
-        n, n_set = len(shreds), len(set_first) - 1
-        first = _c(set_first, np.uint32)
-        codes = np.zeros(max(1, n_set), np.int8)
-        buf, off, sz = pack_payloads([bytes(s) for s in shreds]) if n else (np.zeros(1, np.uint8),) * 3
-        _check(_lib.fd_ed25519_hip_fec_parity_host(self._h, n, _ptr(buf), _ptr(off), _ptr(sz), n_set, _ptr(first), _ptr(codes)))
-        return codes[:n_set], [buf[int(off[i]):int(off[i]) + int(sz[i])].tobytes() for i in range(n)]
+        return self._fec_flat(shreds, set_first, lambda n, buf, off, sz, ns, first, codes: _lib.fd_ed25519_hip_fec_parity_host(
+            self._h, n, buf, off, sz, ns, first, codes))
 
     def fec_parity_host(self, sets):
         """Fills the parity shreds of FEC sets (fd_ed25519_hip_fec_parity_host):
@@ -690,11 +700,7 @@ class Engine:
         (data, then parity, of which the first 0x59 bytes are read) -> (int8
         code per set, the sets with the parity regions written where the code
         is 0); synchronous."""
-        first = [0]
-        for s in sets:
-            first.append(first[-1] + len(s))
-        codes, flat = self.fec_parity_flat([x for s in sets for x in s], first)
-        return codes, [flat[first[k]:first[k + 1]] for k in range(len(sets))]
+        return self._fec_by_sets(sets, self.fec_parity_flat)
 
     def fec_parity_dev(self, n, d_shreds, d_off, d_sz, n_set, d_set_first, d_set_out, stream=None):
         """Device-resident fd_ed25519_hip_fec_parity_dev: device addresses (ints); async."""
@@ -706,16 +712,10 @@ class Engine:
         set k is shreds[set_first[k]:set_first[k + 1]] in tree order, erased
         one flag per slot -> (int8 code per set, the slots after the call);
         synchronous."""
-        from .tile import pack_payloads
-        n, n_set = len(shreds), len(set_first) - 1
-        first = _c(set_first, np.uint32)
-        codes = np.zeros(max(1, n_set), np.int8)
         er = _c([1 if x else 0 for x in erased] + [0], np.uint8)
-        assert len(er) == n + 1
-        buf, off, sz = pack_payloads([bytes(s) for s in shreds]) if n else (np.zeros(1, np.uint8),) * 3
-        _check(_lib.fd_ed25519_hip_fec_recover_host(self._h, n, _ptr(buf), _ptr(off), _ptr(sz), _ptr(er), n_set, _ptr(first),
-                                                    _ptr(codes)))
-        return codes[:n_set], [buf[int(off[i]):int(off[i]) + int(sz[i])].tobytes() for i in range(n)]
+        assert len(er) == len(shreds) + 1
+        return self._fec_flat(shreds, set_first, lambda n, buf, off, sz, ns, first, codes: _lib.fd_ed25519_hip_fec_recover_host(
+            self._h, n, buf, off, sz, _ptr(er), ns, first, codes))
 
     def fec_recover_host(self, sets, erased):
         """Recovers received FEC sets (fd_ed25519_hip_fec_recover_host): sets
@@ -723,11 +723,8 @@ class Engine:
         the list of each set's flags (nonzero: the slot is erased and only
         its length counts) -> (int8 code per set, the sets with the erased
         slots filled where the code is 0); synchronous."""
-        first = [0]
-        for s in sets:
-            first.append(first[-1] + len(s))
-        codes, flat = self.fec_recover_flat([x for s in sets for x in s], [x for e in erased for x in e], first)
-        return codes, [flat[first[k]:first[k + 1]] for k in range(len(sets))]
+        flags = [x for e in erased for x in e]
+        return self._fec_by_sets(sets, lambda flat, first: self.fec_recover_flat(flat, flags, first))
 
     def fec_recover_dev(self, n, d_shreds, d_off, d_sz, d_erased, n_set, d_set_first, d_set_out, stream=None):
         """Device-resident fd_ed25519_hip_fec_recover_dev: device addresses (ints); async."""
