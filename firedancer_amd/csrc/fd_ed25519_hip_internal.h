@@ -691,6 +691,40 @@ typedef struct {
 
 int fd_ed25519_hip_launch_fec_recover( fd_ed25519_fec_recover_params_t const * p, void * stream );
 
+/* ---- shredding entry batches (fd_ed25519_shredder.hip) ---- */
+
+/* front: workgroup q < set_cnt lays out set set0 + q of the call -- it finds
+   the batch that reserved the set in set_first_b, applies fd_shredder_core.h's
+   rules and writes the set's data shreds, parity headers, shred_off, shred_sz
+   and set_first entry; the workgroups behind them judge the batches, a lane
+   each, and close set_first.  The arrays of shreds and sets are the
+   launch's own: entry 0 is shred shred0 and set set0 of the call, so that a
+   host wrapper's pass (a range of the call's sets) is the same launch. */
+typedef struct {
+  uint8_t const *  buf;            /* batch bytes, readable 16 B past buf_sz    */
+  uint64_t         buf_sz;
+  uint64_t const * batch_off;      /* [nb]                                      */
+  uint32_t const * batch_sz;       /* [nb]                                      */
+  void const *     desc;           /* [nb] fd_shredder_core_desc_t, 8-B aligned */
+  uint32_t const * set_first_b;    /* [nb+1] sets of the call                   */
+  uint32_t const * shred_first_b;  /* [nb+1] shreds of the call                 */
+  uint64_t         nb;
+  uint64_t         n_set, n;       /* the call's sets and shreds                */
+  uint64_t         set0, set_cnt;  /* the launch's sets                         */
+  uint64_t         shred0, m;      /* the launch's shreds [shred0, shred0 + m)  */
+  uint64_t         skip_b, skip;   /* batch_off[skip_b] is where byte skip of that batch stands (a pass that continues a batch) */
+  uint8_t *        shreds;         /* shred i of the launch at shreds + base_off + stride i */
+  uint64_t         base_off, stride;
+  uint64_t *       shred_off;      /* [m] out                                   */
+  uint32_t *       shred_sz;       /* [m] preset to 0; out                      */
+  uint32_t *       set_first;      /* [set_cnt+1] out                           */
+  int8_t *         batch_out;      /* [nb] out, or NULL                         */
+  uint8_t const *  privs;          /* [nb][32] 16-B aligned, or NULL            */
+  uint8_t *        keys;           /* [set_cnt][32] out, 16-B aligned, with privs */
+} fd_ed25519_shredder_params_t;
+
+int fd_ed25519_hip_launch_shredder( fd_ed25519_shredder_params_t const * p, void * stream );
+
 /* ---- a block's proof-of-history hash chain (fd_ed25519_poh.hip) ---- */
 
 /* One parameter block for the three launches (fd_poh_core.h's rules):

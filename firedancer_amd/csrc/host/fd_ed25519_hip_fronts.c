@@ -1,8 +1,8 @@
 /* fd_ed25519_hip_fronts.c -- the fronts before the verify phases
-   (include/fd_ed25519_hip.h Parts 2b-2i): stage kernel, verify_common,
+   (include/fd_ed25519_hip.h Parts 2b-2j): stage kernel, verify_common,
    finish kernel in a *_dev; pack, upload, *_dev, download, synchronise in a
    *_host ("The shape of a front"); and the rules the stage
-   kernels run, on the host (*_count, *_plan, *_root, fec_parity, fec_recover, poh, poh_prepare).  Part of the engine:
+   kernels run, on the host (*_count, *_plan, *_root, fec_parity, fec_recover, poh, poh_prepare, shredder).  Part of the engine:
    the *_host wrappers stage in its pinned buffers
    (fd_ed25519_hip_engine_fields.h).  The three wrappers over whole FEC sets
    (fec_seal_host, fec_parity_host, fec_recover_host) share one pass by sets
@@ -23,7 +23,9 @@
 #include "../fd_poh_core.h"
 #include "../fd_front_work.h"
 #include "../fd_fec_pass.h"
+#include "../fd_shredder_core.h"
 
+#include <stddef.h>
 #include <stdlib.h>
 #include <string.h>
 
@@ -1048,3 +1050,217 @@ fd_ed25519_hip_poh_blocks_host( fd_ed25519_hip_engine_t * e, unsigned long nb, u
   return err;
 }
 
+
+/* ---- shredding entry batches (include/fd_ed25519_hip.h Part 2j) -- */
+
+_Static_assert( FD_ED25519_HIP_SHREDDER_OK==FD_SHREDDER_CORE_OK && FD_ED25519_HIP_SHREDDER_ERR_BATCH==FD_SHREDDER_CORE_ERR_BATCH &&
+                FD_ED25519_HIP_SHREDDER_BAD_RESERVATION==FD_SHREDDER_CORE_BAD_RESERVATION,
+                "public and core shredder codes differ" );
+_Static_assert( sizeof(fd_ed25519_hip_shredder_batch_t)==24UL && sizeof(fd_shredder_core_desc_t)==24UL &&
+                offsetof( fd_ed25519_hip_shredder_batch_t, data_idx      )==offsetof( fd_shredder_core_desc_t, data_idx       ) &&
+                offsetof( fd_ed25519_hip_shredder_batch_t, parity_idx    )==offsetof( fd_shredder_core_desc_t, parity_idx     ) &&
+                offsetof( fd_ed25519_hip_shredder_batch_t, version       )==offsetof( fd_shredder_core_desc_t, version        ) &&
+                offsetof( fd_ed25519_hip_shredder_batch_t, parent_off    )==offsetof( fd_shredder_core_desc_t, parent_off     ) &&
+                offsetof( fd_ed25519_hip_shredder_batch_t, reference_tick)==offsetof( fd_shredder_core_desc_t, reference_tick ) &&
+                offsetof( fd_ed25519_hip_shredder_batch_t, block_complete)==offsetof( fd_shredder_core_desc_t, block_complete ),
+                "public and core batch descriptors differ" );
+
+/* the counts and the layout the kernel runs, on the host (no GPU) */
+int
+fd_ed25519_hip_shredder_count( unsigned long sz, unsigned long * n_set, unsigned long * n_data, unsigned long * n_parity ) {
+  if( !n_set || !n_data || !n_parity ) return FD_ED25519_HIP_ERR_INVAL;
+  fd_shredder_core_count( sz, n_set, n_data, n_parity );
+  return FD_ED25519_HIP_OK;
+}
+
+int
+fd_ed25519_hip_shredder( unsigned char const * batch, unsigned long sz, fd_ed25519_hip_shredder_batch_t const * desc,
+                         unsigned char * shreds, unsigned long const * shred_off, unsigned int * shred_sz,
+                         unsigned int * set_first ) {
+  if( !sz ) return FD_ED25519_HIP_SHREDDER_ERR_BATCH;
+  if( !batch || !desc || !shreds || !shred_off || !shred_sz || !set_first ) return FD_ED25519_HIP_ERR_INVAL;
+  return fd_shredder_core_batch( batch, sz, (fd_shredder_core_desc_t const *)desc, shreds, shred_off, shred_sz, set_first );
+}
+
+/* The front's launch behind the memset of its shred_sz and, with work, the
+   parity and the seal over the same arrays on the same stream.  work: the
+   sets' keys [set_cnt][32], the seal's workspace, the parity's codes
+   [set_cnt] -- FD_ED25519_HIP_SHREDDER_WORK_BYTES( m, set_cnt ).  With
+   parity_out the parity's codes go there instead, for a caller who reads them. */
+static int
+shredder_run( fd_ed25519_hip_engine_t * e, fd_ed25519_shredder_params_t * sp, void * work, signed char * parity_out,
+              signed char * set_out, unsigned char * roots, unsigned char * sigs, hipStream_t st ) {
+  uint64_t m = sp->m, ms = sp->set_cnt;
+  uint8_t * keys = (uint8_t *)work, * fec_work = work ? keys + 32UL*ms : NULL;
+  uint8_t * pcodes = parity_out ? (uint8_t *)parity_out : work ? fec_work + FD_ED25519_HIP_FEC_WORK_BYTES( m, ms ) : NULL;
+  int err;
+  if( work && (err = front_work_fits( 32UL*ms + FD_ED25519_HIP_FEC_WORK_BYTES( m, ms ) + ms,
+                                      FD_ED25519_HIP_SHREDDER_WORK_BYTES( m, ms ), "shredder" )) ) return err;
+  /* a shred no set writes has size 0: the parity and the seal judge it without reading it */
+  if( m ) HIPCHK( hipMemsetAsync( sp->shred_sz, 0, 4UL*m, st ), "shredder shred_sz memset" );
+  sp->keys = sp->privs ? keys : NULL;
+  HIPCHK( (hipError_t)fd_ed25519_hip_launch_shredder( sp, st ), "shredder launch" );
+  if( !work ) return FD_ED25519_HIP_OK;
+  if( (err = fd_ed25519_hip_fec_parity_dev( e, m, sp->shreds, (unsigned long const *)sp->shred_off, sp->shred_sz, ms, sp->set_first,
+                                            (signed char *)pcodes, st )) ) return err;
+  return fd_ed25519_hip_fec_seal_dev( e, m, sp->shreds, (unsigned long const *)sp->shred_off, sp->shred_sz, ms, sp->set_first,
+                                      sp->privs ? keys : NULL, fec_work, set_out, roots, sigs, st );
+}
+
+static int
+shredder_dev_impl( fd_ed25519_hip_engine_t * e, unsigned long nb, unsigned char const * buf, unsigned long buf_sz,
+                   unsigned long const * batch_off, unsigned int const * batch_sz, fd_ed25519_hip_shredder_batch_t const * desc,
+                   unsigned int const * set_first_b, unsigned int const * shred_first_b, unsigned long n_set, unsigned long n,
+                   unsigned char * shreds, unsigned long base_off, unsigned long stride, unsigned long * shred_off,
+                   unsigned int * shred_sz, unsigned int * set_first, signed char * batch_out, int seal,
+                   unsigned char const * privs, void * work, signed char * set_out, unsigned char * roots, unsigned char * sigs,
+                   void * stream ) {
+  hipStream_t st;
+  int args_ok = buf && batch_off && batch_sz && desc && set_first_b && shred_first_b && set_first && batch_out &&
+                ( !n || ( shreds && shred_off && shred_sz ) ) && stride>=FD_SHRED_CORE_MAX_SZ && n<=UINT32_MAX && n_set<=INT32_MAX &&
+                nb<=INT32_MAX && !( (uintptr_t)desc & 7UL ) && ( !seal || ( work && set_out && ( privs || !sigs ) ) );
+  int err = front_begin( e, nb, args_ok, seal ? ( (uintptr_t)work | (uintptr_t)privs | (uintptr_t)roots | (uintptr_t)sigs |
+                                                  (uintptr_t)shreds ) : 0UL, "shreds/privs/work/roots/sigs", stream, &st );
+  if( err<=0 ) return err;
+  fd_ed25519_shredder_params_t sp = { 0 };
+  sp.buf = buf; sp.buf_sz = buf_sz; sp.batch_off = (uint64_t const *)batch_off; sp.batch_sz = batch_sz; sp.desc = desc;
+  sp.set_first_b = set_first_b; sp.shred_first_b = shred_first_b; sp.nb = nb; sp.n_set = n_set; sp.n = n;
+  sp.set0 = 0UL; sp.set_cnt = n_set; sp.shred0 = 0UL; sp.m = n; sp.skip_b = UINT64_MAX; sp.skip = 0UL;
+  sp.shreds = shreds; sp.base_off = base_off; sp.stride = stride; sp.shred_off = (uint64_t *)shred_off; sp.shred_sz = shred_sz;
+  sp.set_first = set_first; sp.batch_out = (int8_t *)batch_out; sp.privs = seal ? privs : NULL;
+  return shredder_run( e, &sp, seal ? work : NULL, NULL, set_out, roots, sigs, st );
+}
+
+int
+fd_ed25519_hip_shredder_front_dev( fd_ed25519_hip_engine_t * e, unsigned long nb, unsigned char const * buf, unsigned long buf_sz,
+                                   unsigned long const * batch_off, unsigned int const * batch_sz,
+                                   fd_ed25519_hip_shredder_batch_t const * desc, unsigned int const * set_first_b,
+                                   unsigned int const * shred_first_b, unsigned long n_set, unsigned long n,
+                                   unsigned char * shreds, unsigned long base_off, unsigned long stride,
+                                   unsigned long * shred_off, unsigned int * shred_sz, unsigned int * set_first,
+                                   signed char * batch_out, void * stream ) {
+  return shredder_dev_impl( e, nb, buf, buf_sz, batch_off, batch_sz, desc, set_first_b, shred_first_b, n_set, n, shreds, base_off,
+                            stride, shred_off, shred_sz, set_first, batch_out, 0, NULL, NULL, NULL, NULL, NULL, stream );
+}
+
+int
+fd_ed25519_hip_shredder_dev( fd_ed25519_hip_engine_t * e, unsigned long nb, unsigned char const * buf, unsigned long buf_sz,
+                             unsigned long const * batch_off, unsigned int const * batch_sz,
+                             fd_ed25519_hip_shredder_batch_t const * desc, unsigned int const * set_first_b,
+                             unsigned int const * shred_first_b, unsigned long n_set, unsigned long n, unsigned char * shreds,
+                             unsigned long base_off, unsigned long stride, unsigned long * shred_off, unsigned int * shred_sz,
+                             unsigned int * set_first, signed char * batch_out, unsigned char const * privs, void * work,
+                             signed char * set_out, unsigned char * roots, unsigned char * sigs, void * stream ) {
+  return shredder_dev_impl( e, nb, buf, buf_sz, batch_off, batch_sz, desc, set_first_b, shred_first_b, n_set, n, shreds, base_off,
+                            stride, shred_off, shred_sz, set_first, batch_out, 1, privs, work, set_out, roots, sigs, stream );
+}
+
+/* Pass by pass, cut at set boundaries as fd_fec_pass.h cuts (up to
+   FD_FEC_PASS_CHUNK shreds and as many sets): a pass is a range of the
+   call's sets, and the batches it touches go up as the bytes its sets take --
+   the first from where the pass before stopped in it (the launch's skip), the
+   last up to where this pass stops.  Items: the batch bytes, then from the
+   next 16-byte boundary the pass's shreds FD_SHRED_MAX_SZ apart, which alone
+   come down.  in: keys [nbp][32] (with privs), batch_off u64 [nbp], desc
+   [nbp], set_first_b u32 [nbp+1], shred_first_b u32 [nbp+1], batch_sz u32
+   [nbp] and, device only, shred_off u64 [m], shred_sz u32 [m], set_first u32
+   [ms+1].  out: roots [ms][32], sigs [ms][64], the seal's codes [ms], the
+   parity's codes [ms]. */
+int
+fd_ed25519_hip_shredder_host( fd_ed25519_hip_engine_t * e, unsigned long nb, unsigned char const * batches,
+                              unsigned long const * batch_off, unsigned int const * batch_sz,
+                              fd_ed25519_hip_shredder_batch_t const * desc, unsigned char const * privs,
+                              unsigned char * shreds_out, unsigned long stride, unsigned int * shred_sz_out,
+                              unsigned int * set_first_out, signed char * batch_out, unsigned char * roots, unsigned char * sigs ) {
+  hipStream_t st;
+  int err = front_begin( e, nb, batches && batch_off && batch_sz && desc && shreds_out && shred_sz_out && set_first_out &&
+                                batch_out && stride>=FD_SHRED_CORE_MAX_SZ && nb<=INT32_MAX && ( privs || !sigs ),
+                         0UL, NULL, NULL, &st );
+  if( err<=0 ) return err;
+  err = FD_ED25519_HIP_OK;   /* a call of zero-size batches alone has no pass to set it */
+  /* the reservation: batch b's sets [gs[b], gs[b+1]) and shreds [gh[b], gh[b+1]) of the call */
+  uint32_t * gs = (uint32_t *)malloc( 8UL*( nb+1UL ) ), * gh = gs ? gs + nb + 1UL : NULL;
+  if( !gs ) return FD_ED25519_HIP_ERR_NOMEM;
+  uint64_t N = 0UL, M = 0UL;
+  for( uint64_t b=0UL; b<nb; b++ ) {
+    unsigned long sets, nd, np;
+    fd_shredder_core_count( batch_sz[b], &sets, &nd, &np );
+    batch_out[b] = (signed char)( batch_sz[b] ? FD_ED25519_HIP_SHREDDER_OK : FD_ED25519_HIP_SHREDDER_ERR_BATCH );
+    gs[b] = (uint32_t)N; gh[b] = (uint32_t)M;
+    N += sets; M += nd + np;
+    if( N>INT32_MAX || M>UINT32_MAX ) { free( gs ); return FD_ED25519_HIP_ERR_INVAL; }
+  }
+  gs[nb] = (uint32_t)N; gh[nb] = (uint32_t)M;
+  set_first_out[0] = 0U;
+  uint64_t b = 0UL, q = 0UL, k = 0UL, h = 0UL;   /* the next set: set q of batch b, set k and shred h of the call */
+  while( k<N ) {
+    while( !batch_sz[b] ) b++;
+    /* cut: the sets the pass takes, their shreds and bytes, and the batches [b, b1] they touch */
+    uint64_t b1 = b, q1 = q, ms = 0UL, m = 0UL, bytes = 0UL;
+    while( k+ms<N && ms<FD_FEC_PASS_CHUNK ) {
+      while( q1==gs[b1+1UL]-gs[b1] ) { b1++; q1 = 0UL; }   /* zero-size batches have no sets */
+      fd_shredder_core_plan_t pl;
+      fd_shredder_core_plan( batch_sz[b1], q1, 0U, 0U, &pl );
+      if( m+pl.d+pl.p>FD_FEC_PASS_CHUNK ) break;
+      m += pl.d+pl.p; bytes += pl.bytes; ms++; q1++;
+      set_first_out[ k+ms ] = (uint32_t)( h+m );
+    }
+    if( q1==0UL ) { b1--; q1 = gs[b1+1UL]-gs[b1]; }        /* the pass stopped in front of batch b1: it ends with the one before */
+    uint64_t nbp = b1-b+1UL, shreds_at = ( bytes+15UL ) & ~15UL;
+    uint64_t keys_at = 0UL, off_at = privs ? 32UL*nbp : 0UL, desc_at = off_at + 8UL*nbp, sfb_at = desc_at + 24UL*nbp,
+             hfb_at = sfb_at + 4UL*( nbp+1UL ), sz_at = hfb_at + 4UL*( nbp+1UL ), in_bytes = sz_at + 4UL*nbp,
+             dsoff_at = ( in_bytes+7UL ) & ~7UL, dssz_at = dsoff_at + 8UL*m, dsfirst_at = dssz_at + 4UL*m;
+    if( (err = front_room( e, shreds_at + FD_SHRED_CORE_MAX_SZ*m + 64UL, dsfirst_at + 4UL*( ms+1UL ), 98UL*ms )) ) break;
+    if( (err = grow_dev( &e->d_fr_work, &e->fr_work_cap, FD_ED25519_HIP_SHREDDER_WORK_BYTES( m, ms ) )) ) break;
+    uint64_t pos = 0UL;
+    for( uint64_t c=b; c<=b1; c++ ) {
+      uint64_t from = c==b ? q*FD_SHREDDER_CORE_SET_BYTES : 0UL;
+      uint64_t to   = ( c==b1 && q1<gs[c+1UL]-gs[c] ) ? q1*FD_SHREDDER_CORE_SET_BYTES : batch_sz[c];
+      ( (uint64_t *)( e->h_fr_in + off_at ) )[ c-b ] = pos;
+      ( (uint32_t *)( e->h_fr_in + sz_at  ) )[ c-b ] = batch_sz[c];
+      memcpy( e->h_fr_in + desc_at + 24UL*( c-b ), desc + c, 24UL );
+      if( privs ) memcpy( e->h_fr_in + keys_at + 32UL*( c-b ), privs + 32UL*c, 32UL );
+      if( to>from ) memcpy( e->h_msgs + pos, batches + batch_off[c] + from, to-from );
+      pos += to>from ? to-from : 0UL;
+    }
+    memcpy( e->h_fr_in + sfb_at, gs + b, 4UL*( nbp+1UL ) );
+    memcpy( e->h_fr_in + hfb_at, gh + b, 4UL*( nbp+1UL ) );
+    if( (err = front_upload( e, bytes, in_bytes, st )) ) break;
+    fd_ed25519_shredder_params_t sp = { 0 };
+    sp.buf = e->d_msgs; sp.buf_sz = UINT64_MAX; sp.batch_off = (uint64_t const *)( e->d_fr_in + off_at );
+    sp.batch_sz = (uint32_t const *)( e->d_fr_in + sz_at ); sp.desc = e->d_fr_in + desc_at;
+    sp.set_first_b = (uint32_t const *)( e->d_fr_in + sfb_at ); sp.shred_first_b = (uint32_t const *)( e->d_fr_in + hfb_at );
+    sp.nb = nbp; sp.n_set = N; sp.n = M; sp.set0 = k; sp.set_cnt = ms; sp.shred0 = h; sp.m = m;
+    sp.skip_b = 0UL; sp.skip = q*FD_SHREDDER_CORE_SET_BYTES;
+    sp.shreds = e->d_msgs; sp.base_off = shreds_at; sp.stride = FD_SHRED_CORE_MAX_SZ;
+    sp.shred_off = (uint64_t *)( e->d_fr_in + dsoff_at ); sp.shred_sz = (uint32_t *)( e->d_fr_in + dssz_at );
+    sp.set_first = (uint32_t *)( e->d_fr_in + dsfirst_at ); sp.batch_out = NULL;
+    sp.privs = privs ? e->d_fr_in + keys_at : NULL;
+    uint64_t sigs_at = 32UL*ms, codes_at = 96UL*ms, pcodes_at = 97UL*ms;
+    if( (err = shredder_run( e, &sp, e->d_fr_work, (signed char *)( e->d_fr_out + pcodes_at ),
+                             (signed char *)( e->d_fr_out + codes_at ), e->d_fr_out,
+                             privs ? e->d_fr_out + sigs_at : NULL, st )) ) break;
+    HIPCHK( hipMemcpyAsync( e->h_msgs + shreds_at, e->d_msgs + shreds_at, FD_SHRED_CORE_MAX_SZ*m, hipMemcpyDeviceToHost, st ),
+            "D2H shreds" );
+    if( (err = front_download( e, 98UL*ms, st )) ) break;
+    for( uint64_t i=0UL; i<ms && !err; i++ )
+      if( e->h_fr_out[ pcodes_at+i ] || e->h_fr_out[ codes_at+i ] ) {
+        fd_ed25519_hip_private_set_errorf( "shredder: set %lu got parity code %d, seal code %d", (unsigned long)( k+i ),
+                                           (int)(int8_t)e->h_fr_out[ pcodes_at+i ], (int)(int8_t)e->h_fr_out[ codes_at+i ] );
+        err = FD_ED25519_HIP_ERR_INVAL;
+      }
+    if( err ) break;
+    if( roots ) memcpy( roots + 32UL*k, e->h_fr_out, 32UL*ms );
+    if( sigs )  memcpy( sigs  + 64UL*k, e->h_fr_out + sigs_at, 64UL*ms );
+    for( uint64_t i=0UL; i<m; i++ ) {
+      unsigned char const * s = e->h_msgs + shreds_at + FD_SHRED_CORE_MAX_SZ*i;
+      unsigned sz = ( s[ 0x40 ] & 0xf0 )==0x80 ? FD_SHRED_CORE_MIN_SZ : FD_SHRED_CORE_MAX_SZ;
+      memcpy( shreds_out + stride*( h+i ), s, sz );
+      shred_sz_out[ h+i ] = sz;
+    }
+    k += ms; h += m; b = b1; q = q1;
+    if( q==gs[b+1UL]-gs[b] ) { b++; q = 0UL; }
+  }
+  free( gs );
+  return err;
+}

@@ -255,6 +255,64 @@ def fec_recover(shreds, erased):
     return code, [buf[int(off[i]):int(off[i]) + int(sz[i])].tobytes() for i in range(cnt)]
 
 
+# shredding entry batches (include/fd_ed25519_hip.h Part 2j)
+SHREDDER_OK = 0
+SHREDDER_ERR_BATCH = -19
+SHREDDER_BAD_RESERVATION = -17
+SHREDDER_DESC = np.dtype([("slot", "<u8"), ("data_idx", "<u4"), ("parity_idx", "<u4"), ("version", "<u2"), ("parent_off", "<u2"),
+                          ("reference_tick", "u1"), ("block_complete", "u1"), ("pad", "u1", (2,))])
+assert SHREDDER_DESC.itemsize == 24
+_lib.fd_ed25519_hip_shredder_count.argtypes = [ctypes.c_ulong] + [ctypes.POINTER(ctypes.c_ulong)] * 3
+_lib.fd_ed25519_hip_shredder.argtypes = [_u8p, ctypes.c_ulong] + [_u8p] * 5
+_SHREDDER_FRONT = ([ctypes.c_void_p, ctypes.c_ulong, _u8p, ctypes.c_ulong] + [_u8p] * 5 + [ctypes.c_ulong, ctypes.c_ulong, _u8p,
+                   ctypes.c_ulong, ctypes.c_ulong] + [_u8p] * 4)
+_lib.fd_ed25519_hip_shredder_front_dev.argtypes = _SHREDDER_FRONT + [ctypes.c_void_p]
+_lib.fd_ed25519_hip_shredder_dev.argtypes = _SHREDDER_FRONT + [_u8p] * 5 + [ctypes.c_void_p]
+_lib.fd_ed25519_hip_shredder_host.argtypes = [ctypes.c_void_p, ctypes.c_ulong] + [_u8p] * 6 + [ctypes.c_ulong] + [_u8p] * 5
+
+
+def shredder_work_bytes(n, n_set):
+    """FD_ED25519_HIP_SHREDDER_WORK_BYTES"""
+    return fec_work_bytes(n, n_set) + 33 * int(n_set) + 16
+
+
+def shredder_desc(slot=0, data_idx=0, parity_idx=0, version=0, parent_off=0, reference_tick=0, block_complete=0):
+    """one fd_ed25519_hip_shredder_batch_t; the integer fields narrow as the
+    reference's casts do (idx mod 2^32, version and parent_off mod 2^16)"""
+    d = np.zeros(1, SHREDDER_DESC)
+    d["slot"], d["data_idx"], d["parity_idx"] = slot & (2**64 - 1), data_idx & 0xFFFFFFFF, parity_idx & 0xFFFFFFFF
+    d["version"], d["parent_off"] = version & 0xFFFF, parent_off & 0xFFFF
+    d["reference_tick"], d["block_complete"] = reference_tick & 0xFF, block_complete & 0xFF
+    return d
+
+
+def shredder_count(sz):
+    """fd_ed25519_hip_shredder_count: (sets, data shreds, parity shreds) of a batch of sz bytes"""
+    out = [ctypes.c_ulong() for _ in range(3)]
+    _check(_lib.fd_ed25519_hip_shredder_count(int(sz), *[ctypes.byref(x) for x in out]))
+    return tuple(int(x.value) for x in out)
+
+
+def shredder(batch, desc):
+    """fd_ed25519_hip_shredder: (code, the sets of one batch, each the list of
+    its shreds in tree order -- data shreds whole, parity shreds with header
+    and zero proof and a zero parity region) (host only); desc from
+    shredder_desc."""
+    batch = bytes(batch)
+    n_set, nd, npar = shredder_count(len(batch))
+    n = nd + npar
+    buf = np.zeros(max(1, 1228 * n), np.uint8)
+    off = np.arange(max(1, n), dtype=np.uint64) * 1228
+    sz, first = np.zeros(max(1, n), np.uint32), np.zeros(n_set + 1, np.uint32)
+    src = np.frombuffer(batch or b"\0", np.uint8)
+    code = _lib.fd_ed25519_hip_shredder(_ptr(src), len(batch), _ptr(_c(desc, SHREDDER_DESC)), _ptr(buf), _ptr(off), _ptr(sz),
+                                        _ptr(first))
+    if code:
+        return code, []
+    flat = [buf[1228 * i:1228 * i + int(sz[i])].tobytes() for i in range(n)]
+    return code, [flat[int(first[k]):int(first[k + 1])] for k in range(n_set)]
+
+
 # a block's proof-of-history hash chain (include/fd_ed25519_hip.h Part 2i)
 POH_ERR_PARSE = -16
 POH_UNSUPPORTED = -18
@@ -730,6 +788,49 @@ class Engine:
         """Device-resident fd_ed25519_hip_fec_recover_dev: device addresses (ints); async."""
         _check(_lib.fd_ed25519_hip_fec_recover_dev(self._h, int(n), d_shreds, d_off, d_sz, d_erased, int(n_set), d_set_first,
                                                    d_set_out, stream))
+
+    def shredder_host(self, batches, descs, privs=None, stride=1228):
+        """fd_ed25519_hip_shredder_host: batches a list of entry batches,
+        descs their shredder_desc()s, privs one 32-byte key per batch, one for
+        all, or None -> (int8 code per batch, the call's sets, each the list of
+        its finished shreds, uint8 [n_set, 32] roots, uint8 [n_set, 64]
+        signatures or None); synchronous."""
+        from .tile import pack_payloads
+        nb = len(batches)
+        counts = [shredder_count(len(b)) for b in batches]
+        n_set, n = sum(c[0] for c in counts), sum(c[1] + c[2] for c in counts)
+        buf, off, sz = pack_payloads([bytes(b) for b in batches]) if nb else (np.zeros(1, np.uint8),) * 3
+        desc = np.concatenate([_c(d, SHREDDER_DESC) for d in descs]) if nb else np.zeros(1, SHREDDER_DESC)
+        keys = sigs = None
+        if privs is not None:
+            if isinstance(privs, (bytes, bytearray)):
+                privs = [bytes(privs)] * nb
+            keys = np.frombuffer(b"".join(bytes(k) for k in privs) or bytes(32), np.uint8)
+            sigs = np.zeros((max(1, n_set), 64), np.uint8)
+        out = np.zeros(max(1, stride * n), np.uint8)
+        ssz, first = np.zeros(max(1, n), np.uint32), np.zeros(n_set + 1, np.uint32)
+        codes, roots = np.zeros(max(1, nb), np.int8), np.zeros((max(1, n_set), 32), np.uint8)
+        _check(_lib.fd_ed25519_hip_shredder_host(self._h, nb, _ptr(buf), _ptr(off), _ptr(_c(sz, np.uint32)), _ptr(desc), _ptr(keys),
+                                                 _ptr(out), stride, _ptr(ssz), _ptr(first), _ptr(codes), _ptr(roots), _ptr(sigs)))
+        flat = [out[stride * i:stride * i + int(ssz[i])].tobytes() for i in range(n)]
+        sets = [flat[int(first[k]):int(first[k + 1])] for k in range(n_set)]
+        return codes[:nb], sets, roots[:n_set], (sigs[:n_set] if sigs is not None else None)
+
+    def shredder_front_dev(self, nb, d_buf, buf_sz, d_batch_off, d_batch_sz, d_desc, d_set_first_b, d_shred_first_b, n_set, n,
+                           d_shreds, base_off, stride, d_shred_off, d_shred_sz, d_set_first, d_batch_out, stream=None):
+        """Device-resident fd_ed25519_hip_shredder_front_dev: device addresses (ints); async."""
+        _check(_lib.fd_ed25519_hip_shredder_front_dev(self._h, int(nb), d_buf, int(buf_sz), d_batch_off, d_batch_sz, d_desc,
+                                                      d_set_first_b, d_shred_first_b, int(n_set), int(n), d_shreds, int(base_off),
+                                                      int(stride), d_shred_off, d_shred_sz, d_set_first, d_batch_out, stream))
+
+    def shredder_dev(self, nb, d_buf, buf_sz, d_batch_off, d_batch_sz, d_desc, d_set_first_b, d_shred_first_b, n_set, n,
+                     d_shreds, base_off, stride, d_shred_off, d_shred_sz, d_set_first, d_batch_out, d_privs, d_work, d_set_out,
+                     d_roots=None, d_sigs=None, stream=None):
+        """Device-resident fd_ed25519_hip_shredder_dev (front, parity and seal): device addresses (ints); async."""
+        _check(_lib.fd_ed25519_hip_shredder_dev(self._h, int(nb), d_buf, int(buf_sz), d_batch_off, d_batch_sz, d_desc,
+                                                d_set_first_b, d_shred_first_b, int(n_set), int(n), d_shreds, int(base_off),
+                                                int(stride), d_shred_off, d_shred_sz, d_set_first, d_batch_out, d_privs, d_work,
+                                                d_set_out, d_roots, d_sigs, stream))
 
     def poh_host(self, buf, hdr_off, in_off, sig_first, sig_off, hash_cnt_max=POH_HASH_CNT_CEIL):
         """fd_ed25519_hip_poh_host: (int8 code per microblock, the computed

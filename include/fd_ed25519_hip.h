@@ -215,9 +215,10 @@ typedef struct fd_ed25519_hip_engine fd_ed25519_hip_engine_t;
    Part 2e, the CRDS values of gossip pull responses and push messages; 15:
    Part 2f, sealing a leader's FEC sets; 16: Part 2g, the Reed-Solomon
    parity of a leader's FEC sets; still 16 with Part 2h, recovering received
-   FEC sets, and Part 2i, a block's proof-of-history hash chain: they only
-   add entry points and three codes, and nothing a consumer of version 16
-   was built against has changed).
+   FEC sets, Part 2i, a block's proof-of-history hash chain, and Part 2j,
+   shredding entry batches: they only add entry points, codes and one
+   structure of their own, and nothing a consumer of version 16 was built
+   against has changed).
    A consumer checks
    the library it loaded against the header it was built with:
    fd_ed25519_hip_abi_check( FD_ED25519_HIP_ABI_VERSION,
@@ -1474,6 +1475,211 @@ fd_ed25519_hip_poh_blocks_host( fd_ed25519_hip_engine_t * engine,
                                 signed char *             block_out,
                                 unsigned int *            first_bad,
                                 unsigned char *           out_hash );
+
+/* ---- Part 2j: shredding entry batches ----------------------------------- */
+
+/* The front of the leader's shred path: fd_shredder_init_batch and lines
+   145-221 of fd_shredder_next_fec_set (src/disco/shred/fd_shredder.c) with
+   the fd_shredder_count_* arithmetic (fd_shredder.h:116-145).  An entry
+   batch goes in as its bytes; out come its data shreds and the headers of
+   its parity shreds, laid out as Parts 2g and 2f take them, so that front,
+   parity and seal are fd_shredder as a whole and only the batch bytes ever
+   cross to the device.
+
+   A batch of sz > 0 bytes becomes max( sz, 63679 ) / 31840 FEC sets.  Every
+   set but the last takes 31,840 bytes as 32 data and 32 parity shreds; the
+   last takes the r bytes that remain, 1 <= r <= 63679, as d data shreds --
+   max( 1, ceil( r/1015 ) ) for r <= 9135, ceil( r/995 ) for r <= 31840,
+   ceil( r/975 ) for r <= 62400, else ceil( r/955 ) -- and p parity shreds:
+   the protocol's table of d (17 for 1 ... 32 for 32) in the first two cases,
+   d in the last two.  With depth the proof depth of d + p shreds a data
+   shred carries up to 1115 - 20 depth bytes, and only the batch's last data
+   shred can carry fewer.
+
+   With D the slot index of a set's first data shred and C that of its first
+   parity shred -- the batch's data_idx and parity_idx plus the d and p of
+   the sets before it, mod 2^32; the caller chains them over a slot's batches
+   with shredder_count, which is what fd_shredder_skip_batch does --:
+   data shred i has variant 0x80 | depth, slot, idx D + i, version,
+   fec_set_idx D, parent_off, flags = reference_tick & 0x3f (on the set's last
+   data shred also 0x40 when the set is the batch's last and 0x80 when
+   besides block_complete & 1), size 0x58 + its bytes, the bytes at 0x58 and
+   zeros up to 1203; parity shred j has variant 0x40 | depth, slot, idx
+   C + j, version, fec_set_idx D, data_cnt d, code_cnt p, code.idx j.
+
+   Written, exactly: of a data shred every byte [0, 1203), the signature and
+   proof fields zero; of a parity shred [0, 0x59), the signature zero, and its
+   proof field [1228 - 20 depth, 1228), zero.  The parity region [0x59,
+   0x59 + P) is Part 2g's and is not touched; after parity and seal every
+   byte of every shred is defined.  The leaf prefix the reference parks in
+   the signature field on the way is overwritten by its own signature copy
+   and is not reproduced.  Out of scope: the deshredder, chained and resigned
+   variants, fusing the front into the parity kernel, fd_shred_dest. */
+#define FD_ED25519_HIP_SHREDDER_OK              (  0)
+#define FD_ED25519_HIP_SHREDDER_ERR_BATCH       (-19)   /* sz == 0, or a batch that leaves buf */
+#define FD_ED25519_HIP_SHREDDER_BAD_RESERVATION (-17)   /* the reserved sets and shreds are not shredder_count's */
+
+typedef struct {
+  unsigned long  slot;
+  unsigned int   data_idx;        /* slot index of the batch's first data shred */
+  unsigned int   parity_idx;      /* ... and of its first parity shred */
+  unsigned short version;
+  unsigned short parent_off;
+  unsigned char  reference_tick;
+  unsigned char  block_complete;
+  unsigned char  pad[ 2 ];
+} fd_ed25519_hip_shredder_batch_t;   /* 24 bytes */
+
+/* The sets, data shreds and parity shreds of a batch of sz bytes, host only
+   (fd_shredder_count_fec_sets / _data_shreds / _parity_shreds); zeros for
+   sz == 0.  Returns ERR_INVAL for a missing pointer. */
+int
+fd_ed25519_hip_shredder_count( unsigned long   sz,
+                               unsigned long * n_set,
+                               unsigned long * n_data,
+                               unsigned long * n_parity );
+
+/* One batch, host only (no GPU), from the same source as the device's
+   kernel.  The caller gives shred_off[ i ] for the n_data + n_parity shreds
+   of the batch, in tree order set by set; the call writes shred i at shreds +
+   shred_off[ i ] as said above, shred_sz[ i ] (1203 or 1228) and set_first[ 0
+   .. n_set ].  SHREDDER_ERR_BATCH for sz == 0, nothing written. */
+int
+fd_ed25519_hip_shredder( unsigned char const *                   batch,
+                         unsigned long                           sz,
+                         fd_ed25519_hip_shredder_batch_t const * desc,
+                         unsigned char *                         shreds,
+                         unsigned long const *                   shred_off,
+                         unsigned int *                          shred_sz,
+                         unsigned int *                          set_first );
+
+/* Device-resident batches: every pointer but the engine is a device pointer.
+   Batch b is buf[batch_off[b] .. batch_off[b] + batch_sz[b]) at any byte
+   address; buf must stay readable 16 bytes past buf + buf_sz.  desc is 8-byte
+   aligned.  The caller reserved, from shredder_count, the sets
+   [set_first_b[b], set_first_b[b+1]) of the call's n_set and the shreds
+   [shred_first_b[b], shred_first_b[b+1]) of its n for batch b (both arrays
+   nb + 1 elements): sets in tree order, sets in batch order, batches in call
+   order.  Shred i of the call is written at shreds + base_off + stride i,
+   stride >= 1228, at any alignment, and no byte between shreds changes.  The
+   call also writes shred_off[n] (base_off + stride i), shred_sz[n] and
+   set_first[n_set + 1], so that fec_parity_dev and fec_seal_dev take the
+   same arrays unchanged (their rules for the shred buffer hold: it starts
+   16-byte aligned and stays readable 16 bytes past the last shred).
+   n < 2^32, n_set < 2^31, nb < 2^31.
+
+   batch_out[b] receives SHREDDER_ERR_BATCH for sz == 0 or a batch that
+   leaves buf, else SHREDDER_BAD_RESERVATION for a reservation that runs
+   backwards, leaves [0, n_set) or [0, n) or is not what shredder_count gives
+   for batch_sz[b], else 0.  A batch with a code has no shred written, its
+   shreds' shred_sz are 0 and their shred_off are left alone; of its reserved
+   sets the first gets the whole shred reservation as its range and the
+   others an empty one.  Parts 2g and 2f then give such a set a code without
+   touching anything: FEC_ERR_SET for an empty range and for one of more
+   than FEC_SET_MAX shreds, FEC_ERR_PARSE for the first set of a reservation
+   of 1 to FEC_SET_MAX shreds (set_first is one array of boundaries, so a
+   reservation between two good batches cannot vanish from it).  No other
+   batch's result changes.  A set_first_b or shred_first_b that is no prefix
+   sum is survived: nothing is read or written outside the arrays, a set no
+   batch owns gets the range [n, ...), and a shred no set wrote has
+   shred_sz 0.  Each batch is judged on its own range alone: reservations
+   that are each what shredder_count gives but overlap (shred_first_b
+   0, 18, 0, 18: the first and the third batch, of 1 byte each, both hold
+   [0, 18)) all get code 0 and write the same shreds, whose bytes are then an unspecified mix of theirs -- in bounds,
+   but no such set is fit to send.  Keeping ranges apart is the caller's.
+
+   Asynchronous on `stream` (NULL: the engine's): one launch, behind a
+   memset of shred_sz; no workspace, no allocation, no synchronisation.
+   nb == 0 is a no-op. */
+int
+fd_ed25519_hip_shredder_front_dev( fd_ed25519_hip_engine_t *               engine,
+                                   unsigned long                           nb,
+                                   unsigned char const *                   buf,
+                                   unsigned long                           buf_sz,
+                                   unsigned long const *                   batch_off,
+                                   unsigned int const *                    batch_sz,
+                                   fd_ed25519_hip_shredder_batch_t const * desc,
+                                   unsigned int const *                    set_first_b,
+                                   unsigned int const *                    shred_first_b,
+                                   unsigned long                           n_set,
+                                   unsigned long                           n,
+                                   unsigned char *                         shreds,
+                                   unsigned long                           base_off,
+                                   unsigned long                           stride,
+                                   unsigned long *                         shred_off,
+                                   unsigned int *                          shred_sz,
+                                   unsigned int *                          set_first,
+                                   signed char *                           batch_out,
+                                   void *                                  stream );
+
+/* Device workspace of shredder_dev: the seal's, a private key per set (32)
+   and the parity's code per set (1). */
+#define FD_ED25519_HIP_SHREDDER_WORK_BYTES( n, n_set ) \
+  ( FD_ED25519_HIP_FEC_WORK_BYTES( n, n_set ) + 33UL*(unsigned long)(n_set) + 16UL )
+
+/* Front, parity and seal on one stream: shredder_front_dev's arguments, then
+   privs + 32 b, the private key that signs batch b's sets (the array 16-byte
+   aligned; the front hands each set its batch's key), or NULL for the
+   keyguard split of Part 2f; work, 16-byte aligned,
+   FD_ED25519_HIP_SHREDDER_WORK_BYTES( n, n_set ) bytes; and the seal's
+   set_out, roots and sigs.  Asynchronous, no allocation, no
+   synchronisation. */
+int
+fd_ed25519_hip_shredder_dev( fd_ed25519_hip_engine_t *               engine,
+                             unsigned long                           nb,
+                             unsigned char const *                   buf,
+                             unsigned long                           buf_sz,
+                             unsigned long const *                   batch_off,
+                             unsigned int const *                    batch_sz,
+                             fd_ed25519_hip_shredder_batch_t const * desc,
+                             unsigned int const *                    set_first_b,
+                             unsigned int const *                    shred_first_b,
+                             unsigned long                           n_set,
+                             unsigned long                           n,
+                             unsigned char *                         shreds,
+                             unsigned long                           base_off,
+                             unsigned long                           stride,
+                             unsigned long *                         shred_off,
+                             unsigned int *                          shred_sz,
+                             unsigned int *                          set_first,
+                             signed char *                           batch_out,
+                             unsigned char const *                   privs,
+                             void *                                  work,
+                             signed char *                           set_out,
+                             unsigned char *                         roots,
+                             unsigned char *                         sigs,
+                             void *                                  stream );
+
+/* Host-buffer batches, synchronous, no alignment asked of any argument:
+   batch b is batches[batch_off[b] .. + batch_sz[b]).  Only the batch bytes
+   and the descriptors go up; the finished shreds, roots and signatures come
+   down.  The call makes the reservation itself: shred i of the call, in
+   tree order set by set, batch by batch, is written whole at shreds_out +
+   stride i (stride >= 1228; bytes behind a data shred's 1203 are left
+   alone), shred_sz_out[ i ] is 1203 or 1228, set_first_out has one element
+   more than the call has sets, and batch_out[b] is 0, or SHREDDER_ERR_BATCH
+   for sz == 0: such a batch takes no set and no shred, and a call of such
+   batches alone returns 0 with set_first_out[0] == 0.  The parity's and the
+   seal's codes of every set come down with the shreds and any of them fails
+   the call (they are 0 on sets the front made).  privs as for shredder_dev (NULL: signature fields zero, sigs
+   must be NULL); roots (32 a set) and sigs (64 a set) are optional.  It runs
+   in passes cut at set boundaries (16,384 shreds a pass), so any nb and any
+   batch size fit; a batch larger than a pass is continued in the next. */
+int
+fd_ed25519_hip_shredder_host( fd_ed25519_hip_engine_t *               engine,
+                              unsigned long                           nb,
+                              unsigned char const *                   batches,
+                              unsigned long const *                   batch_off,
+                              unsigned int const *                    batch_sz,
+                              fd_ed25519_hip_shredder_batch_t const * desc,
+                              unsigned char const *                   privs,
+                              unsigned char *                         shreds_out,
+                              unsigned long                           stride,
+                              unsigned int *                          shred_sz_out,
+                              unsigned int *                          set_first_out,
+                              signed char *                           batch_out,
+                              unsigned char *                         roots,
+                              unsigned char *                         sigs );
 
 /* ---- Part 3: batched signing and the synthetic workload generator ------ */
 
