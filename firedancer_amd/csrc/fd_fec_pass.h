@@ -4,7 +4,9 @@
    laid out and how its shreds are packed into the item staging.  Plain C11,
    host only, no HIP: the engine (host/fd_ed25519_hip_fronts.c) stages in its
    pinned buffers through here, and tests/fec_pass_main.c runs the same code
-   under ASan and UBSan on buffers of exactly the sizes stated here.
+   under ASan and UBSan on buffers of exactly the sizes stated here.  Its
+   siblings: fd_shredder_pass.h (fd_ed25519_hip_shredder_host) and
+   fd_poh_pass.h (fd_ed25519_hip_poh_host, _poh_blocks_host).
 
    A pass takes whole sets, up to FD_FEC_PASS_CHUNK shreds and as many sets.
    A set whose range runs backwards, leaves [0, n) or holds more than

@@ -8,7 +8,11 @@
    (fec_seal_host, fec_parity_host, fec_recover_host) share one pass by sets
    -- cut, room, stage; upload; *_dev; download and the front's own copy-back
    -- whose cut, in-block layout and staging are plain C in ../fd_fec_pass.h,
-   held to their buffers under ASan and UBSan by tests/fec_pass_main.c. */
+   held to their buffers under ASan and UBSan by tests/fec_pass_main.c.  The
+   two other wrappers that work pass by pass have the same shape over a header
+   of their own: shredder_host over ../fd_shredder_pass.h
+   (tests/shredder_pass_main.c), poh_host and poh_blocks_host over
+   ../fd_poh_pass.h (tests/poh_pass_main.c). */
 
 #define _GNU_SOURCE
 #include "fd_ed25519_hip_engine_fields.h"
@@ -24,6 +28,8 @@
 #include "../fd_front_work.h"
 #include "../fd_fec_pass.h"
 #include "../fd_shredder_core.h"
+#include "../fd_shredder_pass.h"
+#include "../fd_poh_pass.h"
 
 #include <stddef.h>
 #include <stdlib.h>
@@ -868,96 +874,36 @@ fd_ed25519_hip_poh_dev( fd_ed25519_hip_engine_t * e, unsigned long n, unsigned c
   return FD_ED25519_HIP_OK;
 }
 
-/* signatures per pass of poh_host: 16 MiB of them (a microblock of more travels alone) */
-#define POH_HOST_SIGS (1UL<<18)
-/* an in_off of poh_host_impl with this bit set is an offset into `extra`
-   (poh_blocks_host's in_hash array), not into buf */
-#define POH_IN_EXTRA  (1UL<<63)
+_Static_assert( FD_POH_PASS_CHUNK==FRONT_HOST_CHUNK, "a pass by microblocks is bounded as a pass by items" );
 
-typedef struct { uint64_t k; uint32_t idx; } poh_order_t;
-
-static int
-poh_order_cmp( void const * a, void const * b ) {
-  poh_order_t const * x = (poh_order_t const *)a, * y = (poh_order_t const *)b;
-  if( x->k!=y->k ) return x->k>y->k ? -1 : 1;   /* descending k */
-  return x->idx<y->idx ? -1 : x->idx>y->idx;
-}
-
-/* Judge on the host, order by descending k, then pass by pass: a
-   microblock travels as its header (48), its in state (32) and its
-   signatures (64 each), back to back in the item staging.  in: hdr_off u64
-   [m], in_off u64 [m], sig_off u64 [ns], sig_first u32 [m+1]; out: states
-   [m][32], codes [m]. */
+/* Judge and order, then pass by pass (fd_poh_pass.h): cut, room, stage,
+   upload, poh_dev, download, scatter.  extra: the in states an in_off with
+   FD_POH_PASS_IN_EXTRA points into (poh_blocks_host's in_hash), or NULL. */
 static int
 poh_host_impl( fd_ed25519_hip_engine_t * e, hipStream_t st, unsigned long n, unsigned char const * buf, unsigned long buf_sz,
                unsigned long const * hdr_off, unsigned long const * in_off, unsigned int const * sig_first, unsigned long n_sig,
                unsigned long const * sig_off, unsigned char const * extra, unsigned long hash_cnt_max, signed char * out,
                unsigned char * out_hash ) {
-  poh_order_t * ord = (poh_order_t *)malloc( n*sizeof(poh_order_t) );
+  fd_poh_pass_ord_t * ord = (fd_poh_pass_ord_t *)malloc( n*sizeof(fd_poh_pass_ord_t) );
   if( !ord ) { fd_ed25519_hip_private_set_errorf( "malloc failed" ); return FD_ED25519_HIP_ERR_NOMEM; }
-  uint64_t go = 0UL;
-  for( uint64_t i=0UL; i<n; i++ ) {
-    unsigned long k;
-    int mixin, in_extra = extra && ( in_off[ i ] & POH_IN_EXTRA );
-    /* an in state in `extra` is the caller's own: judged as if it stood at the buffer's start */
-    int code = fd_poh_core_judge( buf, buf_sz, hdr_off[ i ], in_extra ? 0UL : in_off[ i ], sig_first[ i ], sig_first[ i+1UL ],
-                                  n_sig, hash_cnt_max, &k, &mixin );
-    if( code!=FD_POH_CORE_ERR_PARSE )
-      for( uint64_t j=sig_first[ i ]; j<sig_first[ i+1UL ]; j++ )
-        if( !fd_poh_core_inside( sig_off[ j ], 64UL, buf_sz ) ) { code = FD_POH_CORE_ERR_PARSE; break; }
-    if( code==FD_POH_CORE_ERR_PARSE ) {
-      out[ i ] = (signed char)code;
-      if( out_hash ) memset( out_hash + 32UL*i, 0, 32UL );
-      continue;
-    }
-    ord[ go ].k = code ? 0UL : k;   /* an unsupported one travels and is not hashed */
-    ord[ go ].idx = (uint32_t)i;
-    go++;
-  }
-  qsort( ord, go, sizeof(poh_order_t), poh_order_cmp );
+  uint64_t go = fd_poh_pass_order( buf, buf_sz, n, hdr_off, in_off, sig_first, n_sig, sig_off, extra, hash_cnt_max, out, out_hash, ord );
   int err = FD_ED25519_HIP_OK;
-  for( uint64_t a=0UL; a<go && !err; ) {
-    uint64_t b = a, ns = 0UL;
-    for( ; b<go && b-a<FRONT_HOST_CHUNK; b++ ) {
-      uint64_t cnt = (uint64_t)sig_first[ ord[ b ].idx+1UL ] - sig_first[ ord[ b ].idx ];
-      if( b>a && ns+cnt>POH_HOST_SIGS ) break;
-      ns += cnt;
-    }
-    uint64_t m = b-a, bytes = 80UL*m + 64UL*ns;
-    uint64_t in_at = 8UL*m, so_at = 16UL*m, first_at = so_at + 8UL*ns, in_bytes = first_at + 4UL*( m+1UL );
-    if( (err = front_room( e, bytes, in_bytes, 33UL*m )) ) break;
+  for( uint64_t a=0UL, b; a<go; a=b ) {
+    uint64_t ns;
+    b = fd_poh_pass_cut( ord, go, sig_first, a, &ns );
+    uint64_t m = b-a;
+    fd_poh_pass_blocks_t at = fd_poh_pass_blocks( m, ns );
+    if( (err = front_room( e, at.item_bytes, at.in_bytes, at.out_bytes )) ) break;
     if( (err = grow_dev( &e->d_fr_work, &e->fr_work_cap, FD_ED25519_HIP_POH_WORK_BYTES( m, ns ) )) ) break;
-    uint64_t * h_hdr   = (uint64_t *)e->h_fr_in;
-    uint64_t * h_in    = (uint64_t *)( e->h_fr_in + in_at );
-    uint64_t * h_so    = (uint64_t *)( e->h_fr_in + so_at );
-    uint32_t * h_first = (uint32_t *)( e->h_fr_in + first_at );
-    uint64_t pos = 0UL, s = 0UL;
-    for( uint64_t q=0UL; q<m; q++ ) {
-      uint64_t i = ord[ a+q ].idx;
-      int in_extra = extra && ( in_off[ i ] & POH_IN_EXTRA );
-      memcpy( e->h_msgs + pos, buf + hdr_off[ i ], 48UL );
-      memcpy( e->h_msgs + pos + 48UL, in_extra ? extra + ( in_off[ i ] & ~POH_IN_EXTRA ) : buf + in_off[ i ], 32UL );
-      h_hdr[ q ] = pos; h_in[ q ] = pos + 48UL; h_first[ q ] = (uint32_t)s;
-      pos += 80UL;
-      for( uint64_t j=sig_first[ i ]; j<sig_first[ i+1UL ]; j++, s++, pos+=64UL ) {
-        memcpy( e->h_msgs + pos, buf + sig_off[ j ], 64UL );
-        h_so[ s ] = pos;
-      }
-    }
-    h_first[ m ] = (uint32_t)s;
-    if( (err = front_upload( e, bytes, in_bytes, st )) ) break;
-    err = fd_ed25519_hip_poh_dev( e, m, e->d_msgs, bytes, (unsigned long const *)e->d_fr_in,
-                                  (unsigned long const *)( e->d_fr_in + in_at ), (unsigned int const *)( e->d_fr_in + first_at ),
-                                  ns, (unsigned long const *)( e->d_fr_in + so_at ), hash_cnt_max,
-                                  (signed char *)( e->d_fr_out + 32UL*m ), e->d_fr_out, e->d_fr_work, st );
+    fd_poh_pass_stage( buf, hdr_off, in_off, sig_first, sig_off, extra, ord+a, m, &at, e->h_msgs, e->h_fr_in );
+    if( (err = front_upload( e, at.item_bytes, at.in_bytes, st )) ) break;
+    err = fd_ed25519_hip_poh_dev( e, m, e->d_msgs, at.item_bytes, (unsigned long const *)( e->d_fr_in + at.hdr_at ),
+                                  (unsigned long const *)( e->d_fr_in + at.in_at ), (unsigned int const *)( e->d_fr_in + at.first_at ),
+                                  ns, (unsigned long const *)( e->d_fr_in + at.sig_at ), hash_cnt_max,
+                                  (signed char *)( e->d_fr_out + at.codes_at ), e->d_fr_out + at.states_at, e->d_fr_work, st );
     if( err ) break;
-    if( (err = front_download( e, 33UL*m, st )) ) break;
-    for( uint64_t q=0UL; q<m; q++ ) {
-      uint64_t i = ord[ a+q ].idx;
-      out[ i ] = (signed char)e->h_fr_out[ 32UL*m + q ];
-      if( out_hash ) memcpy( out_hash + 32UL*i, e->h_fr_out + 32UL*q, 32UL );
-    }
-    a = b;
+    if( (err = front_download( e, at.out_bytes, st )) ) break;
+    fd_poh_pass_scatter( ord+a, m, &at, e->h_fr_out, out, out_hash );
   }
   free( ord );
   return err;
@@ -1017,7 +963,7 @@ fd_ed25519_hip_poh_blocks_host( fd_ed25519_hip_engine_t * e, unsigned long nb, u
     if( !mb_cnt ) continue;
     unsigned long mb, sg;
     /* sig_first comes back relative to the block's first signature; the block's last element is the next one's first */
-    fd_poh_core_walk( blocks + block_off[ b ], block_sz[ b ], block_off[ b ], POH_IN_EXTRA | ( 32UL*b ), hdr_off + m0, in_off + m0,
+    fd_poh_core_walk( blocks + block_off[ b ], block_sz[ b ], block_off[ b ], FD_POH_PASS_IN_EXTRA | ( 32UL*b ), hdr_off + m0, in_off + m0,
                       sig_first + m0, mb_cnt, sig_off + sg_at, n_sig-sg_at, &mb, &sg );
     for( uint64_t i=m0; i<m0+mb_cnt; i++ ) sig_first[ i ] += (unsigned int)sg_at;
     sg_at += sg;
@@ -1155,17 +1101,10 @@ fd_ed25519_hip_shredder_dev( fd_ed25519_hip_engine_t * e, unsigned long nb, unsi
                             stride, shred_off, shred_sz, set_first, batch_out, 1, privs, work, set_out, roots, sigs, stream );
 }
 
-/* Pass by pass, cut at set boundaries as fd_fec_pass.h cuts (up to
-   FD_FEC_PASS_CHUNK shreds and as many sets): a pass is a range of the
-   call's sets, and the batches it touches go up as the bytes its sets take --
-   the first from where the pass before stopped in it (the launch's skip), the
-   last up to where this pass stops.  Items: the batch bytes, then from the
-   next 16-byte boundary the pass's shreds FD_SHRED_MAX_SZ apart, which alone
-   come down.  in: keys [nbp][32] (with privs), batch_off u64 [nbp], desc
-   [nbp], set_first_b u32 [nbp+1], shred_first_b u32 [nbp+1], batch_sz u32
-   [nbp] and, device only, shred_off u64 [m], shred_sz u32 [m], set_first u32
-   [ms+1].  out: roots [ms][32], sigs [ms][64], the seal's codes [ms], the
-   parity's codes [ms]. */
+/* The reservation, then pass by pass (fd_shredder_pass.h): cut, room, stage,
+   upload, front, parity and seal, download, copy back.  The parity's and the
+   seal's codes of every set come down with the shreds, and any of them fails
+   the call. */
 int
 fd_ed25519_hip_shredder_host( fd_ed25519_hip_engine_t * e, unsigned long nb, unsigned char const * batches,
                               unsigned long const * batch_off, unsigned int const * batch_sz,
@@ -1178,88 +1117,47 @@ fd_ed25519_hip_shredder_host( fd_ed25519_hip_engine_t * e, unsigned long nb, uns
                          0UL, NULL, NULL, &st );
   if( err<=0 ) return err;
   err = FD_ED25519_HIP_OK;   /* a call of zero-size batches alone has no pass to set it */
-  /* the reservation: batch b's sets [gs[b], gs[b+1]) and shreds [gh[b], gh[b+1]) of the call */
-  uint32_t * gs = (uint32_t *)malloc( 8UL*( nb+1UL ) ), * gh = gs ? gs + nb + 1UL : NULL;
-  if( !gs ) return FD_ED25519_HIP_ERR_NOMEM;
-  uint64_t N = 0UL, M = 0UL;
-  for( uint64_t b=0UL; b<nb; b++ ) {
-    unsigned long sets, nd, np;
-    fd_shredder_core_count( batch_sz[b], &sets, &nd, &np );
-    batch_out[b] = (signed char)( batch_sz[b] ? FD_ED25519_HIP_SHREDDER_OK : FD_ED25519_HIP_SHREDDER_ERR_BATCH );
-    gs[b] = (uint32_t)N; gh[b] = (uint32_t)M;
-    N += sets; M += nd + np;
-    if( N>INT32_MAX || M>UINT32_MAX ) { free( gs ); return FD_ED25519_HIP_ERR_INVAL; }
-  }
-  gs[nb] = (uint32_t)N; gh[nb] = (uint32_t)M;
+  uint32_t * gs = (uint32_t *)malloc( 2UL*sizeof(uint32_t)*( nb+1UL ) ), * gh = gs ? gs + nb + 1UL : NULL;
+  if( !gs ) { fd_ed25519_hip_private_set_errorf( "malloc failed" ); return FD_ED25519_HIP_ERR_NOMEM; }
+  uint64_t N, M;
+  if( fd_shredder_pass_reserve( batch_sz, nb, gs, gh, batch_out, &N, &M ) ) { free( gs ); return FD_ED25519_HIP_ERR_INVAL; }
   set_first_out[0] = 0U;
-  uint64_t b = 0UL, q = 0UL, k = 0UL, h = 0UL;   /* the next set: set q of batch b, set k and shred h of the call */
-  while( k<N ) {
-    while( !batch_sz[b] ) b++;
-    /* cut: the sets the pass takes, their shreds and bytes, and the batches [b, b1] they touch */
-    uint64_t b1 = b, q1 = q, ms = 0UL, m = 0UL, bytes = 0UL;
-    while( k+ms<N && ms<FD_FEC_PASS_CHUNK ) {
-      while( q1==gs[b1+1UL]-gs[b1] ) { b1++; q1 = 0UL; }   /* zero-size batches have no sets */
-      fd_shredder_core_plan_t pl;
-      fd_shredder_core_plan( batch_sz[b1], q1, 0U, 0U, &pl );
-      if( m+pl.d+pl.p>FD_FEC_PASS_CHUNK ) break;
-      m += pl.d+pl.p; bytes += pl.bytes; ms++; q1++;
-      set_first_out[ k+ms ] = (uint32_t)( h+m );
-    }
-    if( q1==0UL ) { b1--; q1 = gs[b1+1UL]-gs[b1]; }        /* the pass stopped in front of batch b1: it ends with the one before */
-    uint64_t nbp = b1-b+1UL, shreds_at = ( bytes+15UL ) & ~15UL;
-    uint64_t keys_at = 0UL, off_at = privs ? 32UL*nbp : 0UL, desc_at = off_at + 8UL*nbp, sfb_at = desc_at + 24UL*nbp,
-             hfb_at = sfb_at + 4UL*( nbp+1UL ), sz_at = hfb_at + 4UL*( nbp+1UL ), in_bytes = sz_at + 4UL*nbp,
-             dsoff_at = ( in_bytes+7UL ) & ~7UL, dssz_at = dsoff_at + 8UL*m, dsfirst_at = dssz_at + 4UL*m;
-    if( (err = front_room( e, shreds_at + FD_SHRED_CORE_MAX_SZ*m + 64UL, dsfirst_at + 4UL*( ms+1UL ), 98UL*ms )) ) break;
-    if( (err = grow_dev( &e->d_fr_work, &e->fr_work_cap, FD_ED25519_HIP_SHREDDER_WORK_BYTES( m, ms ) )) ) break;
-    uint64_t pos = 0UL;
-    for( uint64_t c=b; c<=b1; c++ ) {
-      uint64_t from = c==b ? q*FD_SHREDDER_CORE_SET_BYTES : 0UL;
-      uint64_t to   = ( c==b1 && q1<gs[c+1UL]-gs[c] ) ? q1*FD_SHREDDER_CORE_SET_BYTES : batch_sz[c];
-      ( (uint64_t *)( e->h_fr_in + off_at ) )[ c-b ] = pos;
-      ( (uint32_t *)( e->h_fr_in + sz_at  ) )[ c-b ] = batch_sz[c];
-      memcpy( e->h_fr_in + desc_at + 24UL*( c-b ), desc + c, 24UL );
-      if( privs ) memcpy( e->h_fr_in + keys_at + 32UL*( c-b ), privs + 32UL*c, 32UL );
-      if( to>from ) memcpy( e->h_msgs + pos, batches + batch_off[c] + from, to-from );
-      pos += to>from ? to-from : 0UL;
-    }
-    memcpy( e->h_fr_in + sfb_at, gs + b, 4UL*( nbp+1UL ) );
-    memcpy( e->h_fr_in + hfb_at, gh + b, 4UL*( nbp+1UL ) );
-    if( (err = front_upload( e, bytes, in_bytes, st )) ) break;
+  fd_shredder_pass_cur_t cur = { 0UL, 0UL, 0UL, 0UL };
+  while( cur.k<N ) {
+    fd_shredder_pass_t     ps = fd_shredder_pass_cut( batch_sz, gs, N, &cur, set_first_out );
+    fd_shredder_pass_in_t  at = fd_shredder_pass_in( &ps, privs!=NULL );
+    fd_shredder_pass_out_t ot = fd_shredder_pass_out( ps.ms );
+    if( (err = front_room( e, at.item_bytes, at.total, ot.out_bytes )) ) break;
+    if( (err = grow_dev( &e->d_fr_work, &e->fr_work_cap, FD_ED25519_HIP_SHREDDER_WORK_BYTES( ps.m, ps.ms ) )) ) break;
+    uint64_t skip = fd_shredder_pass_stage( batches, batch_off, batch_sz, (fd_shredder_core_desc_t const *)desc, privs, gs, gh, &ps,
+                                            &at, e->h_msgs, e->h_fr_in );
+    if( (err = front_upload( e, ps.bytes, at.in_bytes, st )) ) break;
     fd_ed25519_shredder_params_t sp = { 0 };
-    sp.buf = e->d_msgs; sp.buf_sz = UINT64_MAX; sp.batch_off = (uint64_t const *)( e->d_fr_in + off_at );
-    sp.batch_sz = (uint32_t const *)( e->d_fr_in + sz_at ); sp.desc = e->d_fr_in + desc_at;
-    sp.set_first_b = (uint32_t const *)( e->d_fr_in + sfb_at ); sp.shred_first_b = (uint32_t const *)( e->d_fr_in + hfb_at );
-    sp.nb = nbp; sp.n_set = N; sp.n = M; sp.set0 = k; sp.set_cnt = ms; sp.shred0 = h; sp.m = m;
-    sp.skip_b = 0UL; sp.skip = q*FD_SHREDDER_CORE_SET_BYTES;
-    sp.shreds = e->d_msgs; sp.base_off = shreds_at; sp.stride = FD_SHRED_CORE_MAX_SZ;
-    sp.shred_off = (uint64_t *)( e->d_fr_in + dsoff_at ); sp.shred_sz = (uint32_t *)( e->d_fr_in + dssz_at );
-    sp.set_first = (uint32_t *)( e->d_fr_in + dsfirst_at ); sp.batch_out = NULL;
-    sp.privs = privs ? e->d_fr_in + keys_at : NULL;
-    uint64_t sigs_at = 32UL*ms, codes_at = 96UL*ms, pcodes_at = 97UL*ms;
-    if( (err = shredder_run( e, &sp, e->d_fr_work, (signed char *)( e->d_fr_out + pcodes_at ),
-                             (signed char *)( e->d_fr_out + codes_at ), e->d_fr_out,
-                             privs ? e->d_fr_out + sigs_at : NULL, st )) ) break;
-    HIPCHK( hipMemcpyAsync( e->h_msgs + shreds_at, e->d_msgs + shreds_at, FD_SHRED_CORE_MAX_SZ*m, hipMemcpyDeviceToHost, st ),
+    sp.buf = e->d_msgs; sp.buf_sz = UINT64_MAX; sp.batch_off = (uint64_t const *)( e->d_fr_in + at.off_at );
+    sp.batch_sz = (uint32_t const *)( e->d_fr_in + at.sz_at ); sp.desc = e->d_fr_in + at.desc_at;
+    sp.set_first_b = (uint32_t const *)( e->d_fr_in + at.sfb_at ); sp.shred_first_b = (uint32_t const *)( e->d_fr_in + at.hfb_at );
+    sp.nb = ps.nbp; sp.n_set = N; sp.n = M; sp.set0 = ps.k; sp.set_cnt = ps.ms; sp.shred0 = ps.h; sp.m = ps.m;
+    sp.skip_b = 0UL; sp.skip = skip;
+    sp.shreds = e->d_msgs; sp.base_off = at.shreds_at; sp.stride = FD_SHRED_CORE_MAX_SZ;
+    sp.shred_off = (uint64_t *)( e->d_fr_in + at.shred_off_at ); sp.shred_sz = (uint32_t *)( e->d_fr_in + at.shred_sz_at );
+    sp.set_first = (uint32_t *)( e->d_fr_in + at.set_first_at ); sp.batch_out = NULL;
+    sp.privs = privs ? e->d_fr_in + at.keys_at : NULL;
+    if( (err = shredder_run( e, &sp, e->d_fr_work, (signed char *)( e->d_fr_out + ot.pcodes_at ),
+                             (signed char *)( e->d_fr_out + ot.codes_at ), e->d_fr_out + ot.roots_at,
+                             privs ? e->d_fr_out + ot.sigs_at : NULL, st )) ) break;
+    HIPCHK( hipMemcpyAsync( e->h_msgs + at.shreds_at, e->d_msgs + at.shreds_at, at.shred_bytes, hipMemcpyDeviceToHost, st ),
             "D2H shreds" );
-    if( (err = front_download( e, 98UL*ms, st )) ) break;
-    for( uint64_t i=0UL; i<ms && !err; i++ )
-      if( e->h_fr_out[ pcodes_at+i ] || e->h_fr_out[ codes_at+i ] ) {
-        fd_ed25519_hip_private_set_errorf( "shredder: set %lu got parity code %d, seal code %d", (unsigned long)( k+i ),
-                                           (int)(int8_t)e->h_fr_out[ pcodes_at+i ], (int)(int8_t)e->h_fr_out[ codes_at+i ] );
+    if( (err = front_download( e, ot.out_bytes, st )) ) break;
+    for( uint64_t i=0UL; i<ps.ms && !err; i++ )
+      if( e->h_fr_out[ ot.pcodes_at+i ] || e->h_fr_out[ ot.codes_at+i ] ) {
+        fd_ed25519_hip_private_set_errorf( "shredder: set %lu got parity code %d, seal code %d", (unsigned long)( ps.k+i ),
+                                           (int)(int8_t)e->h_fr_out[ ot.pcodes_at+i ], (int)(int8_t)e->h_fr_out[ ot.codes_at+i ] );
         err = FD_ED25519_HIP_ERR_INVAL;
       }
     if( err ) break;
-    if( roots ) memcpy( roots + 32UL*k, e->h_fr_out, 32UL*ms );
-    if( sigs )  memcpy( sigs  + 64UL*k, e->h_fr_out + sigs_at, 64UL*ms );
-    for( uint64_t i=0UL; i<m; i++ ) {
-      unsigned char const * s = e->h_msgs + shreds_at + FD_SHRED_CORE_MAX_SZ*i;
-      unsigned sz = ( s[ 0x40 ] & 0xf0 )==0x80 ? FD_SHRED_CORE_MIN_SZ : FD_SHRED_CORE_MAX_SZ;
-      memcpy( shreds_out + stride*( h+i ), s, sz );
-      shred_sz_out[ h+i ] = sz;
-    }
-    k += ms; h += m; b = b1; q = q1;
-    if( q==gs[b+1UL]-gs[b] ) { b++; q = 0UL; }
+    if( roots ) memcpy( roots + 32UL*ps.k, e->h_fr_out + ot.roots_at, 32UL*ps.ms );
+    if( sigs )  memcpy( sigs  + 64UL*ps.k, e->h_fr_out + ot.sigs_at,  64UL*ps.ms );
+    fd_shredder_pass_copy_back( e->h_msgs + at.shreds_at, ps.m, shreds_out + stride*ps.h, stride, shred_sz_out + ps.h );
   }
   free( gs );
   return err;

@@ -297,3 +297,21 @@ def test_blocks_host(eng, ed):
     assert [x.tobytes() for x in last] == want_last
     with pytest.raises(ed.HipError):
         eng.poh_blocks_host([cap], [bytes(32)], hash_cnt_max=(1 << 17) + 1)
+
+
+def test_blocks_host_in_several_passes(eng):
+    """poh_blocks_host over more microblocks than a pass takes: 257 copies of
+    the captured block (64 microblocks and 1,280 signatures each), every third
+    one from another in state -- each block's first microblock reads its
+    state from in_hash, in either pass, after the ordering by k.  Every block
+    comes back as the same block and state submitted alone"""
+    cap = util.captured_block()
+    states = [bytes(32), b"\x01" + bytes(31)]
+    alone = [eng.poh_blocks_host([cap], [st]) for st in states]
+    assert [int(a[0][0]) for a in alone] == [0, model.ERR_HASH] and [int(a[1][0]) for a in alone] == [0xFFFFFFFF, 0]
+    pick = [int(b % 3 == 1) for b in range(257)]
+    assert 257 * 64 > 16384 and 257 * 1280 > 1 << 18 and len(set(pick[200:210])) == 2
+    codes, first_bad, last = eng.poh_blocks_host([cap] * 257, [states[p] for p in pick])
+    assert codes.tolist() == [int(alone[p][0][0]) for p in pick]
+    assert first_bad.tolist() == [int(alone[p][1][0]) for p in pick]
+    assert [x.tobytes() for x in last] == [alone[p][2][0].tobytes() for p in pick]

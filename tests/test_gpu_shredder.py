@@ -268,3 +268,37 @@ def test_other_direction(eng, capture_sets):
     assert not codes.any()
     codes, got, _, _ = eng.fec_seal_host(got, None)
     assert not codes.any() and [[bytes(s) for s in st] for st in got] == sets
+
+
+def host_with_keys(eng, ed, oracle, sizes, seed):
+    """shredder_host on seeded batches of these sizes chained in one slot, a
+    key per batch, by digest against the model: shreds, roots, signatures"""
+    batches = [model.seeded_batch(seed + b, sz) for b, sz in enumerate(sizes)]
+    descs, D = [], 0
+    for sz in sizes:
+        descs.append(model.desc(slot=6, data_idx=D, parity_idx=D, version=77, reference_tick=3))
+        D += model.count(sz)[1]
+    keys = util.keys(seed, len(sizes))
+    codes, sets, roots, sigs = eng.shredder_host(batches, [util.ed_desc(ed, d) for d in descs], keys)
+    want = [st for b, d, k in zip(batches, descs, keys) if b for st in model.shred(oracle, b, d, k)]
+    assert codes.tolist() == [0 if sz else model.ERR_BATCH for sz in sizes]
+    assert [len(st) for st in sets] == [len(st) for st in want]
+    assert util.digests(sets) == util.digests(want)
+    assert util.digests([[r.tobytes() for r in roots]]) == util.digests([[fec_model.tree(st)[1] for st in want]])
+    assert util.digests([[s.tobytes() for s in sigs]]) == util.digests([[st[0][:64] for st in want]])
+
+
+def test_host_pass_ends_in_front_of_a_batch_with_keys(eng, ed, oracle):
+    """the first pass of shredder_host stops exactly in front of a batch --
+    122 batches of 63,679 bytes are 16,348 shreds, and the next 134 do not
+    fit -- with a batch of no bytes at the boundary: the second pass starts
+    at a batch that is not the call's first, and signs with that batch's key"""
+    assert model.count(63679) == (1, 67, 67) and 122 * 134 <= 16384 < 123 * 134
+    host_with_keys(eng, ed, oracle, [63679] * 122 + [0, 63679], 383)
+
+
+def test_two_host_passes_with_keys(eng, ed, oracle):
+    """the sizes of test_two_host_passes: the second pass starts inside batch
+    112, whose key both passes sign with"""
+    assert 112 * 134 + 20 * 64 < 16384 < 112 * 134 + 20 * 64 + 134
+    host_with_keys(eng, ed, oracle, [63679] * 112 + [700000] + [63679] * 2, 389)
