@@ -11,7 +11,12 @@
    test_gpu_group_diag.py compare what comes back with Python integers.
 
    Built as libfd_ed25519_diag.so; not linked into the product library and
-   no part of its ABI.
+   no part of its ABI.  The library's other objects, each with an entry
+   point and argument list of its own: fd_ed25519_diag_hash.hip (the SHA-512
+   and SHA-256 headers), fd_ed25519_diag_reedsol.hip (the GF(2^8) product
+   and the recover kernel's coefficients) and fd_ed25519_diag_sign.hip (the
+   signer's family: ge_scalarmult_base, ge_encode and mul256_add over the
+   signer's own [0..128]B table, tests/test_gpu_sign_diag.py).
 
    One C entry point per family,
 

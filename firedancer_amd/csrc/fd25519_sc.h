@@ -12,7 +12,10 @@
    2^252 = -(L - 2^252) = sum m_i 2^(21 i) (mod L),
    m = (666643, 470296, 654183, -997805, 136657, -683901), followed by
    centered carries; two final passes fold the last overflow and
-   canonicalize with floor carries.  Each fold is six v_mad_i64_i32. */
+   canonicalize with floor carries.  Each fold is six v_mad_i64_i32.
+
+   mul256_add is the signer's k a + r before that reduction
+   (fd_ed25519_sign_kernel, fd_ed25519_gen.hip). */
 #pragma once
 #include "fd25519_fe.h"
 
@@ -95,4 +98,27 @@ FD_DEV void sc_reduce512(uint32_t (&out)[8], const uint32_t (&in)[16]) {
   }
 #pragma unroll
   for (int i = 0; i < 8; i++) out[i] = w[i];
+}
+
+/* 256 x 256 -> 512-bit product plus a 256-bit addend */
+FD_DEV void mul256_add(uint32_t (&out)[16], const uint32_t (&a)[8], const uint32_t (&b)[8],
+                       const uint32_t (&c)[8]) {
+#pragma unroll
+  for (int i = 0; i < 16; i++) out[i] = i < 8 ? c[i] : 0u;
+#pragma unroll
+  for (int i = 0; i < 8; i++) {
+    uint64_t carry = 0;
+#pragma unroll
+    for (int j = 0; j < 8; j++) {
+      const uint64_t t = (uint64_t)a[i] * b[j] + out[i + j] + carry;
+      out[i + j] = (uint32_t)t;
+      carry = t >> 32;
+    }
+#pragma unroll
+    for (int j = i + 8; j < 16; j++) {
+      const uint64_t t = (uint64_t)out[j] + carry;
+      out[j] = (uint32_t)t;
+      carry = t >> 32;
+    }
+  }
 }

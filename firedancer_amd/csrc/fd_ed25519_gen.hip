@@ -42,29 +42,6 @@ __global__ void fd_ed25519_fill_random_kernel(uint8_t* d, uint64_t nbytes, uint6
   }
 }
 
-/* 256 x 256 -> 512-bit product plus a 256-bit addend */
-FD_DEV void mul256_add(uint32_t (&out)[16], const uint32_t (&a)[8], const uint32_t (&b)[8],
-                       const uint32_t (&c)[8]) {
-#pragma unroll
-  for (int i = 0; i < 16; i++) out[i] = i < 8 ? c[i] : 0u;
-#pragma unroll
-  for (int i = 0; i < 8; i++) {
-    uint64_t carry = 0;
-#pragma unroll
-    for (int j = 0; j < 8; j++) {
-      const uint64_t t = (uint64_t)a[i] * b[j] + out[i + j] + carry;
-      out[i + j] = (uint32_t)t;
-      carry = t >> 32;
-    }
-#pragma unroll
-    for (int j = i + 8; j < 16; j++) {
-      const uint64_t t = (uint64_t)out[j] + carry;
-      out[j] = (uint32_t)t;
-      carry = t >> 32;
-    }
-  }
-}
-
 __global__ void __launch_bounds__(256)
 fd_ed25519_sign_kernel(fd_ed25519_sign_params_t p) {
   __shared__ int4 s_btab[FD_ED25519_BTAB_INTS / 4];

@@ -404,6 +404,14 @@ int fd_ed25519_hip_private_diag_prep( struct fd_ed25519_hip_engine * e, int form
                                       uint32_t * k, unsigned char * sflag, unsigned char * hflag, unsigned char * pflag,
                                       int32_t * pts, uint32_t * hs, uint32_t * perm, signed char * out, uint32_t * fix );
 
+/* diagnostic (tests/test_gpu_sign_diag.py): the engine's [0..128]B table of
+   36-int entries (y+x, y-x, 2dxy, six zeros), copied back on the engine's
+   stream.  fd_ed25519_sign_kernel alone reads this table (the verify
+   kernels take btab16 and btabw), so check_base_tables and base_entry do
+   not see it; the test holds it against the curve and hands it to
+   libfd_ed25519_diag.so's sign family. */
+int fd_ed25519_hip_private_sign_table( struct fd_ed25519_hip_engine * e, int out[ FD_ED25519_BTAB_INTS ] );
+
 /* The device hashes take a message's remaining byte count as a signed
    32-bit value (fd_sha512_dev.h sha_msg_dword: (int)sz - p), so a message
    the device hashes is at most FD_ED25519_HIP_MSG_SZ_MAX (2^31 - 1) bytes.

@@ -93,6 +93,7 @@ _lib.fd_ed25519_hip_private_diag_prep.argtypes = [ctypes.c_void_p, ctypes.c_int,
 _lib.fd_ed25519_hip_private_diag_prep_nmax.argtypes = [ctypes.c_void_p, ctypes.c_int]
 _lib.fd_ed25519_hip_private_diag_prep_nmax.restype = ctypes.c_ulong
 _lib.fd_ed25519_hip_private_diag_prep_check.argtypes = [ctypes.c_int, ctypes.c_ulong, ctypes.c_ulong, ctypes.c_ulong] + [_u8p] * 6
+_lib.fd_ed25519_hip_private_sign_table.argtypes = [ctypes.c_void_p, ctypes.c_void_p]
 _lib.fd_ed25519_hip_verify_digests_dev.argtypes = [ctypes.c_void_p, ctypes.c_ulong] + [_u8p] * 5
 _lib.fd_ed25519_hip_strerror.argtypes = [ctypes.c_int]
 _lib.fd_ed25519_hip_strerror.restype = ctypes.c_char_p
@@ -904,6 +905,14 @@ class Engine:
         out = (ctypes.c_int * 30)()
         _check(_lib.fd_ed25519_hip_engine_base_entry(self._h, which, index, out))
         return np.array(out[:], dtype=np.int64)
+
+    def sign_table(self):
+        """Diagnostic: the signer's own table [0..128]B, int32 [129][36] =
+        (y+x, y-x, 2dxy) in radix-2^25.5 limbs and six zero words an entry
+        (fd_ed25519_hip_private_sign_table; sign_dev and gen_dev alone read it)"""
+        out = np.zeros((129, 36), dtype=np.int32)
+        _check(_lib.fd_ed25519_hip_private_sign_table(self._h, out.ctypes.data))
+        return out
 
     def diag_half_scalars(self, k_words):
         """Diagnostic: the device's half-size scalar search for k given as

@@ -13,6 +13,7 @@ every intermediate is checked against the machine type it lives in.
 
 The group-level functions mirror fd25519_ge.h and the dsm loop of
 fd_ed25519_kernels.hip (dsm_half_one / dsm_full_one / table_build), and
+the signer's ge_scalarmult_base of fd25519_dsm.h (sign_base_loop), and
 the exponentiation chain mirrors fe_pow22523.  Feeding the loop its own
 outputs until the intervals stop growing shows the bounds hold for every
 iteration, whatever the inputs (tests/test_bounds.py).
@@ -415,6 +416,49 @@ def dsm_half_loop(max_iter=6):
             return Q, it
         Q = Qn if Q is None else {k: fe_hull(Q[k], Qn[k]) for k in Q}
     return Q, max_iter
+
+
+def tight():
+    """fd25519_fe.h "tight": every limb within 1.01 units, either sign"""
+    return [(-int(1.01 * (1 << (w - 1))), int(1.01 * (1 << (w - 1)))) for w in W]
+
+
+def sign_entry():
+    """an entry of the signer's [0..128]B table as ge_scalarmult_base hands
+    it to ge_madd: three tight fields (gen_btab: carried sums and a centered
+    product; tests/test_gpu_sign_diag.py holds the table itself to that),
+    either digit sign"""
+    return precomp_cneg({"yplusx": tight(), "yminusx": tight(), "xy2d": tight()})
+
+
+def sign_base_loop(max_iter=6):
+    """ge_scalarmult_base (fd25519_dsm.h): the identity plus an entry, then
+    per digit eight ge_p2_dbl with their conversions, ge_p1p1_to_p3, ge_madd
+    with an entry of either sign and ge_p1p1_to_p2, fed its own output until
+    the intervals stop growing.  Returns the fixed point of Q (the ge_p2 the
+    function returns and ge_encode takes), the iteration that reached it and
+    the trace: (callee, argument) for every call, for the contracts'
+    check in tests/test_bounds.py"""
+    ent, trace = sign_entry(), []
+
+    def call(name, f, *args):
+        trace.append((name, args))
+        return f(*args)
+
+    Q = call("ge_p1p1_to_p2", p1p1_to_p2, call("ge_madd", ge_madd, identity_p3(), ent))
+    for it in range(max_iter):
+        q = Q
+        for dd in range(8):
+            Rt = call("ge_p2_dbl", p2_dbl, q)
+            if dd < 7:
+                q = call("ge_p1p1_to_p2", p1p1_to_p2, Rt)
+        P = call("ge_p1p1_to_p3", p1p1_to_p3, Rt, False, False)
+        Qn = call("ge_p1p1_to_p2", p1p1_to_p2, call("ge_madd", ge_madd, P, ent))
+        Qh = ge_hull(Q, Qn)
+        if Qh == Q:
+            return Q, it, trace
+        Q = Qh
+    return Q, max_iter, trace
 
 
 def dsm_full_loop(max_iter=6):

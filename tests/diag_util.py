@@ -6,8 +6,9 @@ radix-2^25.5 form and the lane-split radix-2^16 form, and the operand
 classes (limb vectors at the documented bounds, special values in several
 representations, scalar edge lists); and for the hash family
 (diag/fd_ed25519_diag_hash.hip) the byte-buffer layout, the case builders
-and hashlib's digests in the word order the device returns.  Test
-infrastructure, no product code.
+and hashlib's digests in the word order the device returns; and the call
+of the sign family (diag/fd_ed25519_diag_sign.hip), whose cases and model
+are tests/sign_model.py's.  Test infrastructure, no product code.
 
 Everything here is exact: Python integers, no tolerances."""
 import ctypes
@@ -45,6 +46,9 @@ FAMILIES = {  # family -> (ops, words in per case, words out per case)
     "fe": (FE_OPS, 20, 20), "r16": (R16_OPS, 32, 32), "sc": (SC_OPS, 16, 64), "digits160": (("digits",), 11, 80),
     "ge": (GE_OPS, 80, 40), "ge4": (GE4_OPS, 80, 40), "ge16": (GE16_OPS, 128, 64),
 }
+# diag/fd_ed25519_diag_sign.hip: a family with one more argument, the signer's table (Diag.run_sign)
+SIGN_OPS = ("base", "base_wide", "muladd", "encode")
+SIGN_IN, SIGN_OUT = 32, 40
 HIP_ERROR_INVALID_VALUE = 1
 
 
@@ -62,6 +66,29 @@ class Diag:
         self.lib.fd_ed25519_diag_hash.argtypes = [ctypes.c_int, ctypes.c_void_p, ctypes.c_ulong, ctypes.c_void_p,
                                                   ctypes.c_void_p, ctypes.c_ulong]
         self.lib.fd_ed25519_diag_hash.restype = ctypes.c_int
+        self.lib.fd_ed25519_diag_sign.argtypes = [ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_ulong,
+                                                  ctypes.c_void_p]
+        self.lib.fd_ed25519_diag_sign.restype = ctypes.c_int
+
+    def raw_sign(self, opnum, inp, out, n, btab):
+        """fd_ed25519_diag_sign as it is: inp / out uint32 arrays, btab an int32 array or None; the HIP error code"""
+        return self.lib.fd_ed25519_diag_sign(int(opnum), inp.ctypes.data, out.ctypes.data, int(n),
+                                             None if btab is None else btab.ctypes.data)
+
+    def run_sign(self, op, rows, btab=None):
+        """run() for the sign family: btab is Engine.sign_table() (ops base and base_wide)"""
+        n = len(rows)
+        inp = np.zeros((max(n, 1), SIGN_IN), dtype=np.uint32)
+        for i, r in enumerate(rows):
+            assert len(r) <= SIGN_IN
+            inp[i, :len(r)] = [int(v) & 0xffffffff for v in r]
+        out = np.zeros((max(n, 1), SIGN_OUT), dtype=np.uint32)
+        if btab is not None:
+            btab = np.ascontiguousarray(btab, dtype=np.int32)
+            assert btab.size == 129 * 36
+        rc = self.raw_sign(SIGN_OPS.index(op), inp, out, n, btab)
+        assert rc == 0, f"fd_ed25519_diag_sign({op}) returned HIP error {rc}"
+        return out[:n].astype(np.int64)
 
     def raw_hash(self, opnum, buf, inp, out, n, buf_sz=None):
         """fd_ed25519_diag_hash as it is: buf a uint8 array, inp / out uint32 arrays; the HIP error code"""

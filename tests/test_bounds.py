@@ -67,6 +67,39 @@ def test_dsm_loop_fixed_point(loop):
         _within(Q[k], -0.001, 2.001)
 
 
+def test_sign_base_loop_fixed_point():
+    """ge_scalarmult_base's chain reaches a fixed point, and every call in it
+    gets what the callee's header comment accepts (fd25519_ge.h, units of
+    fd25519_fe.h; an "unsigned [0, 2x]" product's top limbs exceed two units
+    by the carry join, hence 2.001 as in the dsm loops above):
+      ge_p2_dbl      |X|, |Y|, |Z| <= 2x
+      ge_p1p1_to_*   X, Z, T within 3x (19-sides: 3.3x is the hard limit), Y within [-1x, 4x]
+      ge_madd        p.X, p.Y, p.T and p.Z centered products (tight: 1.01x), the entry tight"""
+    Q, iters, trace = bm.sign_base_loop()
+    assert iters < 6, "intervals did not converge"
+    for k in "XYZ":
+        _within(Q[k], -0.001, 2.001)
+    assert {name for name, _ in trace} == {"ge_p2_dbl", "ge_p1p1_to_p2", "ge_p1p1_to_p3", "ge_madd"}
+    for name, args in trace:
+        p = args[0]
+        if name == "ge_p2_dbl":
+            for k in "XYZ":
+                _within(p[k], -2.001, 2.001)
+        elif name == "ge_madd":
+            for k in "XYZT":
+                _within(p[k], -1.01, 1.01)
+            for k in ("yplusx", "yminusx", "xy2d"):
+                _within(args[1][k], -1.01, 1.01)
+        else:
+            for k in "XZT":
+                _within(p[k], -3.04, 3.04)
+            _within(p["Y"], -1.01, 4.04)
+    # the chain is the function's: 1 + 1 calls before the loop, then 8 + 7 + 1 + 1 + 1 a digit
+    per_digit = [name for name, _ in trace[2:20]]
+    assert per_digit.count("ge_p2_dbl") == 8 and per_digit.count("ge_p1p1_to_p2") == 8
+    assert per_digit.count("ge_p1p1_to_p3") == 1 and per_digit.count("ge_madd") == 1
+
+
 def test_formula_choices_are_needed():
     """the alternatives the kernels avoid do overflow: (X+Y)^2 of unsigned
     coordinates, and 2dT from a -2dT table as a 19-side"""
